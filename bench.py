@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X ORB front-end hot path (BASELINE.json metric, config C2 at N=1).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`);
+--dump-outputs DIR also writes the last timed step's outputs as DIR/<name>.npy.  --full adds every
+other measurement to the line (the extra fields below and the other workloads' sections).
 
 One "step" = ORBextractor::operator() on one batch of 64 synthetic 640x480 frames (nFeatures 1000,
 8 levels, scale 1.2, FAST 20/7), device-resident inputs and outputs, on each rank's GPU.  Frames are
 independent units: each rank extracts its own batch (weak scaling, no data-path collective).
 `value` = keypoints extracted+described by all ranks per ms of the max-over-ranks timed region.
 
-Extra fields: `roofline` for the dominant kernel (HIP-event time on the launch stream, algorithmic
+Extra fields (--full): `roofline` for the dominant kernel (HIP-event time on the launch stream, algorithmic
 bytes per DESIGN.md), `cpu_baseline` (the CPU oracle -- a restatement of the reference -- timed on
 this host's cores on a bounded sample), `stages_ms` (per-stage HIP-event ms per step).
 """
@@ -1177,6 +1181,38 @@ def pmc_traffic():
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, kps, desc, counts):
+    """--dump-outputs: what the last timed step handed its caller, as float32 arrays under `dirpath`:
+    keypoints.npy [F, cap, 7] (cv::KeyPoint fields; octave and class_id, int32 in the record, by value),
+    descriptors.npy [F, cap, 32], counts.npy [F, 2] (keypoints, monoIndex), frames.npy [F] (the frames'
+    rows in the step's output).  Rows past a frame's keypoint count are never written by the
+    extraction and are stored as zeros.  An output above 64 MB (several ranks' gathered blocks) is
+    cut to a fixed, seeded choice of frames."""
+    import numpy as np
+    d = pathlib.Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    k, ds, cnt = kps.cpu().numpy(), desc.cpu().numpy(), counts.cpu().numpy()
+    nfr, cap = k.shape[0], k.shape[1]
+    keep = np.arange(nfr)
+    fit = DUMP_LIMIT_BYTES // (4 * (cap * (7 + 32) + 3))
+    if nfr > fit:
+        keep = np.sort(np.random.default_rng(0).choice(nfr, fit, replace=False))
+    k, ds, cnt = k[keep], ds[keep], cnt[keep]
+    live = np.arange(cap)[None, :] < cnt[:, :1]
+    kf = k.astype(np.float32)
+    kf[..., 5:] = k.view(np.int32)[..., 5:]
+    kf[~live] = 0
+    df = ds.astype(np.float32)
+    df[~live] = 0
+    np.save(d / "keypoints.npy", kf)
+    np.save(d / "descriptors.npy", df)
+    np.save(d / "counts.npy", cnt.astype(np.float32))
+    np.save(d / "frames.npy", keep.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1187,6 +1223,14 @@ def main():
                     help="extractor handles with a batch in flight, each on its own stream (consecutive steps "
                          "overlap: one batch's latency-bound quad-tree/describe tail runs beside the next "
                          "batch's pyramid/FAST); 1 = one batch at a time")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (keypoints, descriptors, "
+                         "counts) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-stage and per-launch kernel "
+                         "times and the roofline, the CPU baselines, LocalBA, stereo, PoseOptimization, BoW, the "
+                         "matchers, the tracking chain, single-frame latency, PCIe-inclusive C2 and C4 (the "
+                         "--no-* options and --launch-dump select among these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-ba", action="store_true", help="skip the LocalBA (C5) measurement")
@@ -1203,6 +1247,9 @@ def main():
     ap.add_argument("--launch-dump", default=None,
                     help="write the timed region's per-launch kernel durations (JSON) to this path")
     args = ap.parse_args()
+    if args.launch_dump and not args.full:
+        ap.error("--launch-dump records passes that only --full runs")
+    full = args.full
 
     import numpy as np
     import torch
@@ -1273,20 +1320,21 @@ def main():
     if (counts[:, 1] < 0).any():
         raise RuntimeError("a frame exceeded the keypoint capacity")
 
-    # per-stage breakdown (HIP events at every stage boundary) in an untimed pass: one batch at a
-    # time on handle 0, so the stage times are those of a single batch
-    ex.profile(True)
-    for _ in range(min(10, args.steps)):
-        ex.extract_batch_device(imgs, (0, 1000), cap=cap, out=out, stream=streams[0])
-    torch.cuda.synchronize(dev)
-    stage_ms, launches, _ = ex.stage_ms()
-    ex.profile(False)
-    # latency of one batch alone (no batch in flight beside it), untimed for `value`
-    t1 = time.perf_counter()
-    for _ in range(min(10, args.steps)):
-        ex.extract_batch_device(imgs, (0, 1000), cap=cap, out=out, stream=streams[0])
+    if full:
+        # per-stage breakdown (HIP events at every stage boundary) in an untimed pass: one batch at a
+        # time on handle 0, so the stage times are those of a single batch
+        ex.profile(True)
+        for _ in range(min(10, args.steps)):
+            ex.extract_batch_device(imgs, (0, 1000), cap=cap, out=out, stream=streams[0])
         torch.cuda.synchronize(dev)
-    single_ms = (time.perf_counter() - t1) * 1e3 / min(10, args.steps)
+        stage_ms, launches, _ = ex.stage_ms()
+        ex.profile(False)
+        # latency of one batch alone (no batch in flight beside it), untimed for `value`
+        t1 = time.perf_counter()
+        for _ in range(min(10, args.steps)):
+            ex.extract_batch_device(imgs, (0, 1000), cap=cap, out=out, stream=streams[0])
+            torch.cuda.synchronize(dev)
+        single_ms = (time.perf_counter() - t1) * 1e3 / min(10, args.steps)
     # untimed steps for at least ORB_BENCH_SETTLE_MS (default 300 ms) so the GPU clocks have left
     # their idle state: the timed region of the default 20 steps lasts only ~5 ms
     settle_s = float(os.environ.get("ORB_BENCH_SETTLE_MS", "300")) * 1e-3
@@ -1304,12 +1352,53 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
+    last = outs[(it[0] - 1) % H]  # the last step's outputs (sharded: every rank's, gathered)
     if sharded is not None:
-        sharded.finish()
+        last = sharded.finish()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     elapsed_ms = (time.perf_counter() - t0) * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+
+    total_feats = feats_per_step * args.steps
+    if world > 1:
+        t = torch.tensor([elapsed_ms], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed_ms = float(t.item())
+        f = torch.tensor([total_feats], dtype=torch.int64, device=dev)
+        dist.all_reduce(f, op=dist.ReduceOp.SUM)
+        total_feats = int(f.item())
+    result = {
+        "metric": "ORB features/ms (640x480, 8-level) + LocalBA iter ms @1/2/4/8 GPU",
+        "value": round(total_feats / elapsed_ms, 3),
+        "unit": "features/ms",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed_ms / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (polygon frames, seeds 100..163; no EuRoC images ship with the reference)",
+        "config": {"workload": "C2: batch of 64 synthetic 640x480 frames per GPU, nFeatures=1000, 8 levels, "
+                               "extraction+description (ORBextractor::operator())",
+                   "frames_per_gpu": nfr, "width": WIDTH, "height": HEIGHT, "nfeatures": NFEAT,
+                   "nlevels": NLEVELS, "features_per_step_per_gpu": feats_per_step,
+                   "batches_in_flight": H,
+                   "parallelism": f"frame-sharded x{world}" + (
+                       f", all-gather of descriptors+keypoints ({backend})" if world > 1 else "")},
+    }
+    if not full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beside the headline figure
     # the same steps again, every handle recording an HIP event pair on each stage kernel's dispatch
     # (hipExtLaunchKernel: the dispatch's own begin / end, on its stream): the roofline's launch
     # durations.  (A separate pass: the event pairs on every launch cost the timed region ~5 %.)
@@ -1350,15 +1439,6 @@ def main():
     excl_ms = {(pyr_kernel if k == "k_pyramid_level" else k): v for k, v in excl_ms.items()}
     launch_ms = {(pyr_kernel if k == "k_pyramid_level" else k): v for k, v in launch_ms.items()}
     pyr_launch_avg_ms = sum(excl_ms[pyr_kernel]) / max(1, len(excl_ms[pyr_kernel]))
-
-    total_feats = feats_per_step * args.steps
-    if world > 1:
-        t = torch.tensor([elapsed_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed_ms = float(t.item())
-        f = torch.tensor([total_feats], dtype=torch.int64, device=dev)
-        dist.all_reduce(f, op=dist.ReduceOp.SUM)
-        total_feats = int(f.item())
 
     if rank == 0:
         per_step = {k: v / max(1, launches) for k, v in stage_ms.items()}
@@ -1425,26 +1505,8 @@ def main():
                   "path_bytes_over_step_le_peak": bool(path_gbs <= HBM_PEAK_GBS)}
         if not (checks["dominant_kernel_ms_per_step_le_step"] and checks["path_bytes_over_step_le_peak"]):
             raise RuntimeError(f"roofline cross-check failed: {checks}, {dom_k} {dk}")
-        result = {
-            "metric": "ORB features/ms (640x480, 8-level) + LocalBA iter ms @1/2/4/8 GPU",
-            "value": round(total_feats / elapsed_ms, 3),
-            "unit": "features/ms",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed_ms / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (polygon frames, seeds 100..163; no EuRoC images ship with the reference)",
-            "config": {"workload": "C2: batch of 64 synthetic 640x480 frames per GPU, nFeatures=1000, 8 levels, "
-                                   "extraction+description (ORBextractor::operator())",
-                       "frames_per_gpu": nfr, "width": WIDTH, "height": HEIGHT, "nfeatures": NFEAT,
-                       "nlevels": NLEVELS, "features_per_step_per_gpu": feats_per_step,
-                       "batches_in_flight": H, "single_batch_ms": round(single_ms, 4),
-                       "parallelism": f"frame-sharded x{world}" + (
-                           f", all-gather of descriptors+keypoints ({backend})" if world > 1 else "")},
+        result["config"]["single_batch_ms"] = round(single_ms, 4)
+        result.update({
             "stages_ms": {k: round(v, 4) for k, v in per_step.items()},
             "roofline": {"bound": "hbm", "kernel": dom_k, "achieved": round(dom_ach, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(dom_ach / HBM_PEAK_GBS, 5),
@@ -1474,7 +1536,7 @@ def main():
                                  "pair on every dispatch in a pass of the timed region's batches one at a time (bench.py --launch-dump writes them; "
                                  "profiles/r06/launch_durations_*.json); traffic = PMC FETCH_SIZE x2 + WRITE_SIZE per "
                                  "launch (profiles/pmc_latest.json)"},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             from oracle import oracle as oracle_mod
             result["cpu_baseline"] = cpu_baseline(oracle_mod, frames[: min(nfr, 32)], args.cpu_budget)

@@ -2433,7 +2433,8 @@ struct orb_ba_s {
     DevBuf<double> red_buf;
     // sharded device-driven loop: this rank's partials (all-reduced out of place into the solve's
     // buffers: a gated no-op unit re-reduces unchanged partials into unchanged sums) and the stop flag
-    // the host raises for the trial controller (pinned)
+    // the host raises for the trial controller (pinned: [0] the flag, [1 + (u & 1)] the state's `done`
+    // as unit u left it, copied down behind the unit's last launch)
     DevBuf<double> dpart;
     int32_t* h_stop = nullptr;
     bool force_dist = false;  // ORBGPU_BA_DIST_FORCE=1 with a one-rank RCCL communicator (tests)
@@ -2497,7 +2498,7 @@ int orb_ba_create(orb_ba_t* out) {
         hipStreamCreateWithFlags(&h->tail, hipStreamNonBlocking) != hipSuccess ||
         hipHostMalloc(&h->h_scal, 8 * sizeof(double), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&h->h_prog, sizeof(LmProgress), hipHostMallocDefault) != hipSuccess || !h->lm.grow(1) ||
-        hipHostMalloc(&h->h_stop, sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc(&h->h_stop, 3 * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
         hipEventCreateWithFlags(&h->unit_ev[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->unit_ev[1], hipEventDisableTiming) != hipSuccess) {
         delete h;
@@ -3215,8 +3216,16 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
             } else {
                 for (int r = 0; r < units_per_launch; ++r) unit_launches();
             }
+            // sharded: the ranks must launch the same number of units (each one issues collectives).
+            // The pinned progress is written by the unit's last kernel, which may or may not have run
+            // when the host looks at it one unit later; `done` as this unit left it is the same on
+            // every rank.
+            if (dist && hipMemcpyAsync(&h->h_stop[1 + (u & 1)], &L->done, sizeof(int32_t), hipMemcpyDeviceToHost, s) !=
+                            hipSuccess)
+                return false;
             return hipEventRecord(h->unit_ev[u & 1], s) == hipSuccess;
         };
+        auto done_after = [&](int u) -> bool { return dist ? h->h_stop[1 + (u & 1)] != 0 : h->h_prog->done != 0; };
         const int max_units = (std::max(0, opt->iterations) * 10 + units_per_launch - 1) / units_per_launch;
         if (max_units > 0) {
             if (!unit(0)) return orbgpu_fail(ORB_ERR_DEVICE, "BA launch failed");
@@ -3226,7 +3235,7 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
                 if (hipEventSynchronize(h->unit_ev[(u - 1) & 1]) != hipSuccess)
                     return orbgpu_fail(ORB_ERR_DEVICE, "BA device error");
                 if (trace && n_unit_t < 32) unit_t[n_unit_t++] = us(t_pack, clk::now());
-                if (h->h_prog->done && more) {
+                if (done_after(u - 1) && more) {
                     // the solve ended inside unit u-1 and unit u, queued behind it, is a run of gated
                     // no-op launches: the restore and the results go on the tail stream beside it
                     if (hipStreamWaitEvent(h->tail, h->unit_ev[(u - 1) & 1], 0) != hipSuccess)
@@ -3234,7 +3243,7 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
                     rs = h->tail;
                 }
                 if (!coll_ok) return orbgpu_fail(ORB_ERR_DEVICE, "BA collective failed");
-                if (h->h_prog->done || !more) break;
+                if (done_after(u - 1) || !more) break;
                 // (the queued unit is live: the tail stays on s; sharded, the ranks agree on the stop on
                 // the device instead, so that every rank launches the same collectives)
                 if (!dist && stop_requested(opt)) break;

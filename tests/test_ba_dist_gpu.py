@@ -52,9 +52,26 @@ def _run(world, kw):
     procs = [ctx.Process(target=_worker, args=(r, world, port, kw, q)) for r in range(world)]
     for p in procs:
         p.start()
-    out = dict(q.get(timeout=300) for _ in procs)
-    for p in procs:
-        p.join(timeout=60)
+    import queue
+    import time
+    out = {}
+    t0 = time.time()
+    try:
+        while len(out) < world:  # a crashed worker fails the test instead of blocking on the queue
+            try:
+                r, v = q.get(timeout=5)
+                out[r] = v
+            except queue.Empty:
+                dead = [p.exitcode for p in procs if p.exitcode not in (None, 0)]
+                assert not dead, f"workers exited with {dead}"
+                assert time.time() - t0 < 300, "workers timed out"
+        for p in procs:
+            p.join(timeout=60)
+    finally:
+        for p in procs:  # (ranks left waiting in a collective for one that is gone)
+            if p.is_alive():
+                p.kill()
+                p.join(timeout=10)
     for r, v in out.items():
         assert not isinstance(v, str), f"rank {r}: {v}"
     return out

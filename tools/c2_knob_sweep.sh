@@ -3,7 +3,7 @@
 #   tools/c2_knob_sweep.sh "ENV=.. ENV2=.." "..."   (each argument one setting; "-" = defaults)
 set -u
 O=gpurun_out/knobs; mkdir -p $O
-EX="--no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
+EX="--full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
 for r in 1 2; do
   for cfg in "$@"; do
     if [ "$cfg" = "-" ]; then envs=""; else envs="$cfg"; fi

@@ -1,6 +1,6 @@
 set -u
 O=gpurun_out/c3ab; mkdir -p $O
-EX="--no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers"
+EX="--full --no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers"
 for h in 1 3 1 3; do
   ORB_C3_INFLIGHT=$h timeout -k 10 300 python3 bench.py $EX > $O/h$h.json 2> $O/h$h.err || { echo fail; tail -5 $O/h$h.err; exit 1; }
   python3 -c "

@@ -5,7 +5,7 @@
 set -u
 O=gpurun_out/c3q; mkdir -p $O
 : > $O/sweep.txt
-EX="--no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
+EX="--full --no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
 for q in 4 8 16; do
   for h in 1 2 3 4 5; do
     GPU_MAX_HW_QUEUES=$q ORB_C3_INFLIGHT=$h timeout -k 10 200 python3 bench.py $EX > $O/q${q}_h$h.json 2> $O/q${q}_h$h.err || { echo "q$q h$h failed"; tail -5 $O/q${q}_h$h.err; exit 1; }

@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/c4_inflight; mkdir -p $O
 : > $O/sweep.txt
-EX="--no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-matchers --no-chain"
+EX="--full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-matchers --no-chain"
 for pass in 1 2; do
   for h in ${@:-3 4 6 8}; do
     timeout -k 10 200 python3 bench.py $EX --in-flight $h > $O/h$h.json 2> $O/h$h.err || { echo "in-flight $h failed"; tail -5 $O/h$h.err; exit 1; }

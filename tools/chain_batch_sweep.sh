@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/chain_sweep; mkdir -p $O
 : > $O/sweep.txt
-EX="--no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --steps 10"
+EX="--full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --steps 10"
 for pass in 1 2; do
   for cfg in ${@:-256:1 256:2 512:1 512:2}; do
     nb=${cfg%:*}; nbuf=${cfg#*:}

@@ -4,7 +4,7 @@
 set -u
 export TMPDIR=/tmp
 O=gpurun_out/paff; mkdir -p $O
-EX="--no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
+EX="--full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
 if [ "${1:-}" != pmc ]; then
 timeout -k 10 400 python -u -m pytest tests/test_extract_gpu.py tests/test_workloads_gpu.py -x -q --timeout 200 --timeout-method thread > $O/tests.log 2>&1 || { tail -20 $O/tests.log; exit 1; }
 tail -1 $O/tests.log

@@ -6,8 +6,8 @@ set -u
 export TMPDIR=/tmp
 O=gpurun_out/round
 mkdir -p $O
-EX="--no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers"
-timeout -k 10 400 python3 bench.py --launch-dump $O/launch_durations.json > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+EX="--full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers"
+timeout -k 10 400 python3 bench.py --full --launch-dump $O/launch_durations.json > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py $EX --launch-dump $O/stats_launch_durations.json > $O/stats_bench.json 2> $O/stats.log || { echo "stats failed"; exit 1; }
 # the last 20 steps' dispatches = bench.py's instrumented pass (the roofline's per-launch durations)
 : > $O/timed_kernel_avg.txt

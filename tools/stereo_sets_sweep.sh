@@ -4,7 +4,7 @@
 set -u
 O=gpurun_out/stereo_sets; mkdir -p $O
 : > $O/sweep.txt
-EX="--no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
+EX="--full --no-cpu-baseline --no-ba --no-pose --no-bow --no-single --no-c4 --no-matchers --no-chain"
 for pass in 1 2; do
   for h in ${@:-1 2 3}; do
     ORB_STEREO_SETS=$h timeout -k 10 200 python3 bench.py $EX > $O/h$h.json 2> $O/h$h.err || { echo "$h failed"; tail -5 $O/h$h.err; exit 1; }

@@ -14,7 +14,7 @@ for v in "$@"; do
   fi
   echo "$v: $(tail -1 $O/t_$v.log)"
   for rep in 1 2; do
-    if ! timeout -k 10 120 python bench.py --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --steps 30 > $O/b_$v.json 2>$O/b_$v.err; then
+    if ! timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-ba --no-stereo --no-pose --no-bow --no-single --no-c4 --no-matchers --steps 30 > $O/b_$v.json 2>$O/b_$v.err; then
       echo "$v: bench failed"; tail $O/b_$v.err; status=1; break 2
     fi
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['ms_per_step'], d['config']['single_batch_ms'], d['stages_ms'])" $O/b_$v.json $v
