@@ -10,15 +10,24 @@
 //   Hll (3x3 per landmark), b, Dinv, Z = Hpl Dinv, S (dense n x n, n = 6 * free poses), x.
 // Host-built structure (once per call, g2o's buildStructure): Hessian indices (free poses by id,
 // then landmarks by id), landmark -> edges CSR (pose rows ascending) and pose -> (landmark, edge)
-// lists in landmark order; the landmarks two poses share are found on the device (k_ba_schur_blocks).
+// lists in landmark order; the landmarks two poses share are found on the device (k_ba_schur_pairs).
 //
-// One LM iteration = k_ba_build (per edge: error, Huber weight, Jacobians, quadratic form parts)
-// -> k_ba_reduce_land / k_ba_reduce_pose (fixed-order reductions) -> per trial:
-// k_ba_schur_edges (Dinv, Z, Hpl*db per edge) -> k_ba_schur_blocks (S = Hpp + lambda I - sum Z Hpl^T,
-// one wave per 6x6 block) -> k_ba_schur_rhs -> k_ba_chol (single-workgroup blocked Cholesky + both
-// triangular solves) -> k_ba_backsub (x_l) -> k_ba_update (push + oplus) -> k_ba_error -> k_ba_sums
-// (robust chi2 and g2o's computeScale).  The host reads two scalars per trial and runs g2o's
-// accept / reject logic (rejection restores the backup, like g2o's pop()).
+// The LM loop runs on the device: g2o's accept / reject logic is in the last block of the trial's
+// kernel (lm_trial_done; a rejected trial's estimate is replaced from the backup by the next trial,
+// like g2o's pop()), the per-trial kernels gate themselves on the LmState, and the host only keeps
+// two "units" (one LM trial each, several per captured graph) in flight and reads a pinned progress
+// record.  Two units exist:
+//   fast unit, 4 launches (one process, n <= 288): k_u_land_build (landmark-major: per edge error,
+//     Huber weight, Jacobians, quadratic form parts at the start of an iteration; Hll / b_l, Dinv,
+//     Z = Hpl Dinv, Hpl Dinv b_l) -> k_u_schur2 (S = -sum Z Hpl^T one wave per 6x6 block, b_S, Hpp /
+//     b_p) -> k_ba_chol_mf2 (single-workgroup MFMA Cholesky + both triangular solves, adding
+//     Hpp + lambda I as it loads S) -> k_u_land_trial (x_l, push + oplus, errors at the new estimate,
+//     robust chi2, g2o's computeScale, the trial controller);
+//   6-launch unit (sharded solves, n > 288, ORBGPU_BA_FAST_UNIT=0): k_u_edges_build -> k_u_reduce_build
+//     (fixed-order reductions, build controller) -> k_ba_schur_edges -> k_u_schur -> k_ba_chol_mf2 or
+//     k_ba_chol_rows (tile rows over many workgroups, + k_u_pose_update beyond 64 free poses) ->
+//     k_u_land_trial; sharded, an all-reduce follows the reductions, the Schur complement and the
+//     trial's sums, with the controllers in k_lm_build_ctl / k_lm_trial_ctl.
 //
 // Reductions run in a fixed order, so results are deterministic; they differ from g2o's serial
 // sums by rounding only (parity bar: 1e-6 RMSE on poses).  S is factored with Cholesky; Eigen's
@@ -38,6 +47,7 @@
 #include <cstring>
 #include <limits>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 #include "ba_structure.h"
@@ -79,26 +89,19 @@ static_assert(sizeof(EdgeDev) == sizeof(orb_ba_edge_t), "edge layout");
 struct LmState {
     double lambda, ni, current_chi, ini_chi, final_chi, initial_chi, user_lambda, tau;
     int32_t it, qmax, nbad, phase, done, reject, terminated, trials, iterations;
-    int32_t lin;  // which half of the double-buffered Hpl holds the current linearisation
 };
 // what the host reads after each unit (pinned)
 struct LmProgress {
     double final_chi, initial_chi, lambda;
     int32_t done, it, trials, terminated;
 };
-enum { kGateBuild = 0, kGateBuild0 = 1, kGateTrial = 2, kGateRestore = 3 };
-
-// Hpl is double-buffered on the device-driven path: every trial linearises at its new estimate into
-// the other half, which becomes current when the trial is accepted (the next iteration's build
-// then has nothing left to compute).  Host-driven path (no state): the first half.
-__device__ __forceinline__ size_t hpl_cur(const LmState* st, size_t alt) { return st && st->lin ? alt : 0; }
+// what a kernel is part of: the build (the start of an iteration only), the trial, the final restore
+enum { kGateBuild = 0, kGateTrial = 2, kGateRestore = 3 };
 
 __device__ __forceinline__ bool lm_skip(const LmState* st, int kind) {
-    if (!st) return false;
     if (kind == kGateRestore) return !st->reject;
     if (st->done) return true;
     if (kind == kGateBuild) return st->phase != 0;
-    if (kind == kGateBuild0) return st->phase != 0 || st->it != 0;
     return false;
 }
 
@@ -270,20 +273,10 @@ __device__ __forceinline__ double ba_edge(int e, const EdgeDev* __restrict__ edg
     return rho0;
 }
 
-template <bool kBuild>
-__global__ __launch_bounds__(kT) void k_ba_edges(int ne, const EdgeDev* __restrict__ edges,
-                                                 const orb_ba_camera_t* __restrict__ cams,
-                                                 const double* __restrict__ pose, const double* __restrict__ point,
-                                                 const int32_t* __restrict__ pose_h, Huber2 hub,
-                                                 double* __restrict__ err, double* __restrict__ rho0_out,
-                                                 double* __restrict__ ecl, double* __restrict__ hpl,
-                                                 double* __restrict__ ecp, const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    const int e = blockIdx.x * kT + threadIdx.x;
-    if (e < ne) ba_edge<kBuild>(e, edges, cams, pose, point, pose_h, hub, err, rho0_out, ecl, hpl, ecp, 0);
-}
-
-// Hll and b_l per landmark: sum of its edges in edge order (g2o accumulates in edge id order)
+// Hll and b_l per landmark, as the 6-launch (and sharded) unit sums them: one thread adds the landmark's
+// edges in edge order (g2o accumulates in edge id order).  The fast unit (k_u_land_build) instead sums
+// them as kLB lane-strided partials joined by a shuffle tree, so the two units' Hll / b_l differ by
+// rounding; both are held to the oracle at the 1e-6 bar.
 __device__ __forceinline__ double ba_reduce_land(int l, const int32_t* __restrict__ off, const int32_t* __restrict__ eidx,
                                                const double* __restrict__ ecl, double* __restrict__ hll,
                                                double* __restrict__ bl) {
@@ -311,15 +304,6 @@ __device__ __forceinline__ double ba_reduce_land(int l, const int32_t* __restric
     for (int i = 0; i < 9; ++i) hll[9 * (size_t)l + i] = s[i];
     for (int i = 0; i < 3; ++i) bl[3 * (size_t)l + i] = s[9 + i];
     return fmax(fmax(fabs(s[0]), fabs(s[4])), fabs(s[8]));  // computeLambdaInit's part of this landmark
-}
-
-__global__ __launch_bounds__(kT) void k_ba_reduce_land(int nl, const int32_t* __restrict__ off,
-                                                       const int32_t* __restrict__ eidx, const double* __restrict__ ecl,
-                                                       double* __restrict__ hll, double* __restrict__ bl,
-                                                       const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    const int l = blockIdx.x * kT + threadIdx.x;
-    if (l < nl) (void)ba_reduce_land(l, off, eidx, ecl, hll, bl);
 }
 
 // Sum of 64 lanes' partials of NC values, lane c < NC adding value c's partials in lane order
@@ -387,32 +371,6 @@ __device__ __forceinline__ double ba_reduce_pose(int p, int lane, const int32_t*
     return t;  // value `lane`'s total (lanes < 42)
 }
 
-__global__ __launch_bounds__(64) void k_ba_reduce_pose(const int32_t* __restrict__ off, const LandEdge* __restrict__ eidx,
-                                                       const double* __restrict__ ecp, double* __restrict__ hpp,
-                                                       double* __restrict__ bp, const LmState* __restrict__ lm_st,
-                                                       int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    ba_reduce_pose(blockIdx.x, threadIdx.x, off, eidx, ecp, hpp, bp);
-}
-
-// max |diag| over the free vertices' Hessian blocks (computeLambdaInit)
-__global__ __launch_bounds__(kT) void k_ba_maxdiag(int nf, int nl, const double* __restrict__ hpp,
-                                                   const double* __restrict__ hll, double* __restrict__ out,
-        const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    __shared__ double red[kT];
-    double m = 0;
-    for (int i = threadIdx.x; i < 6 * nf; i += kT) m = fmax(m, fabs(hpp[36 * (size_t)(i / 6) + 7 * (i % 6)]));
-    for (int i = threadIdx.x; i < 3 * nl; i += kT) m = fmax(m, fabs(hll[9 * (size_t)(i / 3) + 4 * (i % 3)]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = kT / 2; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = red[0];
-}
-
 __device__ __forceinline__ void inverse3(const double m[9], double o[9]) {  // Eigen closed form
     auto cof = [&](int i, int j) {
         const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
@@ -435,10 +393,9 @@ __device__ __forceinline__ void land_dinv(const double* __restrict__ hll, int l,
 __global__ __launch_bounds__(kT) void k_ba_schur_edges(int nfe, const double* __restrict__ lam, const int32_t* __restrict__ fedge,
                                                        const int32_t* __restrict__ fland, const double* __restrict__ hll,
                                                        const double* __restrict__ bl, const double* __restrict__ hpl,
-                                                       size_t hpl_alt, double* __restrict__ z, double* __restrict__ cb,
-        const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    hpl += hpl_cur(lm_st, hpl_alt);
+                                                       double* __restrict__ z, double* __restrict__ cb,
+                                                       const LmState* __restrict__ st) {
+    if (lm_skip(st, kGateTrial)) return;
     const double lambda = *lam;
     const int t = blockIdx.x * kT + threadIdx.x;
     if (t >= nfe) return;
@@ -582,17 +539,6 @@ __device__ __forceinline__ void ba_schur_block(int blk, int lane, int n, int nf,
     S[(size_t)(6 * j + c) * n + 6 * i + r] = v;
 }
 
-
-__global__ __launch_bounds__(64) void k_ba_schur_blocks(int n, int nf, const double* __restrict__ lam, int add_diag,
-                                                        const int32_t* __restrict__ blk_off,
-                                                        const EdgePair* __restrict__ pairs, const int32_t* __restrict__ cnt,
-                                                        const double* __restrict__ z, const double* __restrict__ hpl,
-                                                        const double* __restrict__ hpp, double* __restrict__ S,
-                                                        const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    ba_schur_block(blockIdx.x, threadIdx.x, n, nf, *lam, add_diag, blk_off, pairs, cnt, z, hpl, hpp, S);
-}
-
 // b_S = b_p - sum over the pose's edges of Hpl_e db (one wave per free pose; the indices of up to 8
 // edges per lane first, then their 6 values each, all in flight)
 __device__ __forceinline__ void ba_schur_rhs(int p, int lane, const int32_t* __restrict__ off,
@@ -620,14 +566,6 @@ __device__ __forceinline__ void ba_schur_rhs(int p, int lane, const int32_t* __r
     }
     const double t = wave_sum_cols<6>(s, lane);
     if (lane < 6) bs[6 * (size_t)p + lane] = (use_bp ? bp[6 * (size_t)p + lane] : 0.0) - t;
-}
-
-__global__ __launch_bounds__(64) void k_ba_schur_rhs(const int32_t* __restrict__ off, const LandEdge* __restrict__ eidx,
-                                                     const double* __restrict__ cb, const double* __restrict__ bp,
-                                                     int use_bp, double* __restrict__ bs, const LmState* __restrict__ lm_st,
-                                                     int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    ba_schur_rhs(blockIdx.x, threadIdx.x, off, eidx, cb, bp, use_bp, bs);
 }
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
@@ -967,12 +905,12 @@ template <int W>
 __global__ __launch_bounds__((W + 1) * 64) void k_ba_chol_mf2(int n, const double* __restrict__ S,
                                                               const double* __restrict__ b, double* __restrict__ x,
                                                               int32_t* __restrict__ status, int64_t* __restrict__ trace,
-                                                              const LmState* __restrict__ lm_st, int lm_gk,
+                                                              const LmState* __restrict__ lm_st,
                                                               const double* __restrict__ hpp_add, const double* __restrict__ lam_add) {
-    if (lm_skip(lm_st, lm_gk)) return;
+    if (lm_skip(lm_st, kGateTrial)) return;
     constexpr int SL = (kMfMaxNT * (kMfMaxNT + 1) / 2 + W - 1) / W;
     // hpp_add (the fast unit, k_u_schur2): S holds -sum Z Hpl^T only; element (row, col) of a diagonal 6x6
-    // block gains Hpp + lambda I here, in the value k_ba_schur_block would have stored there (its mirror
+    // block gains Hpp + lambda I here, in the value ba_schur_block would have stored there (its mirror
     // store, lane (col % 6, row % 6), is the one that lands): (0 - sum) + (Hpp + lambda) = (Hpp + lambda) - sum
     const double lam_d = hpp_add ? *lam_add : 0.0;
     // Only tiles (i, j) with i - j <= 1 hold diagonal 6x6 blocks (6 < 16), so only they read Hpp (a
@@ -1280,7 +1218,7 @@ __global__ __launch_bounds__(256) void k_u_pose_update(PoseTail pt, const double
                                                        const LmState* __restrict__ st) {
     if (lm_skip(st, kGateTrial)) return;
     __shared__ double cs[256];
-    const bool rej = st && st->reject;
+    const bool rej = st->reject != 0;
     double c = 0.0;  // thread t: poses t, t + 256, ... in order
     for (int t = threadIdx.x; t < pt.nf; t += 256) c += pose_tail_one(pt, t, pt.free_pose[t], x + 6 * (size_t)t, rej);
     cs[threadIdx.x] = c;
@@ -1353,8 +1291,8 @@ __global__ __launch_bounds__(kRowThreads) void k_ba_chol_rows(int n, const doubl
                                                               int32_t* __restrict__ status, double* __restrict__ lpub,
                                                               double* __restrict__ ypub, unsigned* __restrict__ cflag,
                                                               double* __restrict__ racc,
-                                                              const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
+                                                              const LmState* __restrict__ lm_st) {
+    if (lm_skip(lm_st, kGateTrial)) return;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int NT = (n + 15) >> 4;
     const int i = blockIdx.x;
@@ -1546,110 +1484,19 @@ __device__ __forceinline__ void ba_backsub(int l, int n, double lambda, const in
     }
 }
 
-__global__ __launch_bounds__(kT) void k_ba_backsub(int nl, int n, const double* __restrict__ lam,
-                                                   const int32_t* __restrict__ off, const int32_t* __restrict__ eidx,
-                                                   const int32_t* __restrict__ erow, const double* __restrict__ hpl,
-                                                   const double* __restrict__ bl, const double* __restrict__ hll,
-                                                   double* __restrict__ x, const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    const int l = blockIdx.x * kT + threadIdx.x;
-    double xl[3];
-    if (l < nl) ba_backsub(l, n, *lam, off, eidx, erow, hpl, bl, hll, x, xl);
-}
-
-// push + oplus for every free vertex: threads [0, nf) poses, [nf, nf + nl) landmarks
-// push + oplus for vertex t (poses first, then landmarks).  from_bak: the previous trial was
-// rejected and not restored yet (device-driven loop): start from the backup and keep it.
-__device__ __forceinline__ void ba_update(int t, int nf, int nl, int n, bool from_bak,
-                                          const int32_t* __restrict__ free_pose, const int32_t* __restrict__ land_point,
-                                          const double* __restrict__ x, double* __restrict__ pose,
-                                          double* __restrict__ pose_bak, double* __restrict__ point,
-                                          double* __restrict__ point_bak) {
-    if (t < nf) {
-        double* T = pose + 7 * (size_t)free_pose[t];
-        double* Tb = pose_bak + 7 * (size_t)free_pose[t];
-        double v[7], u[6];
-        for (int i = 0; i < 7; ++i) {
-            v[i] = from_bak ? Tb[i] : T[i];
-            Tb[i] = v[i];
-        }
-        for (int i = 0; i < 6; ++i) u[i] = x[6 * (size_t)t + i];
-        se3_oplus(v, u);
-        for (int i = 0; i < 7; ++i) T[i] = v[i];
-    } else if (t < nf + nl) {
-        const int l = t - nf;
-        double* X = point + 3 * (size_t)land_point[l];
-        double* Xb = point_bak + 3 * (size_t)land_point[l];
-        for (int i = 0; i < 3; ++i) {
-            const double v = from_bak ? Xb[i] : X[i];
-            Xb[i] = v;
-            X[i] = v + x[n + 3 * (size_t)l + i];
-        }
-    }
-}
-
-__global__ __launch_bounds__(kT) void k_ba_update(int nf, int nl, int n, const int32_t* __restrict__ free_pose,
-                                                  const int32_t* __restrict__ land_point, const double* __restrict__ x,
-                                                  double* __restrict__ pose, double* __restrict__ pose_bak,
-                                                  double* __restrict__ point, double* __restrict__ point_bak,
-                                                  const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    ba_update(blockIdx.x * kT + threadIdx.x, nf, nl, n, false, free_pose, land_point, x, pose, pose_bak, point,
-              point_bak);
-}
-
+// after the last unit: a rejected last trial is undone from the backup (threads [0, nf) poses, then landmarks)
 __global__ __launch_bounds__(kT) void k_ba_restore(int nf, int nl, const int32_t* __restrict__ free_pose,
                                                    const int32_t* __restrict__ land_point, double* __restrict__ pose,
                                                    const double* __restrict__ pose_bak, double* __restrict__ point,
                                                    const double* __restrict__ point_bak,
-        const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
+                                                   const LmState* __restrict__ st) {
+    if (lm_skip(st, kGateRestore)) return;
     const int t = blockIdx.x * kT + threadIdx.x;
     if (t < nf) {
         for (int i = 0; i < 7; ++i) pose[7 * (size_t)free_pose[t] + i] = pose_bak[7 * (size_t)free_pose[t] + i];
     } else if (t < nf + nl) {
         const int l = t - nf;
         for (int i = 0; i < 3; ++i) point[3 * (size_t)land_point[l] + i] = point_bak[3 * (size_t)land_point[l] + i];
-    }
-}
-
-// out[0] = sum rho0 (activeRobustChi2), out[1] = sum x (lambda x + b) (computeScale, before +1e-3)
-// out: [0] robust chi2, [1] computeScale part, [2] factorisation status (as a double), [3] max diag
-// (written earlier by k_ba_maxdiag).  host: optional pinned copy of out[0..3] (one process: the
-// host reads it after the stream sync, no copy launches).
-__global__ __launch_bounds__(1024) void k_ba_sums(int ne, const double* __restrict__ rho0, int x0, int nx, const double* __restrict__ lam,
-                                                  const double* __restrict__ x, const double* __restrict__ b,
-                                                  const int32_t* __restrict__ status, double* __restrict__ out,
-                                                  double* __restrict__ host,
-        const LmState* __restrict__ lm_st, int lm_gk) {
-    if (lm_skip(lm_st, lm_gk)) return;
-    const double lambda = *lam;
-    __shared__ double r0[1024], r1[1024];
-    double a = 0, c = 0;
-    for (int i = threadIdx.x; i < ne; i += 1024) a += rho0[i];
-    if (x)
-        for (int i = x0 + threadIdx.x; i < nx; i += 1024) c += x[i] * (lambda * x[i] + b[i]);
-    r0[threadIdx.x] = a;
-    r1[threadIdx.x] = c;
-    __syncthreads();
-    for (int w = 512; w >= 1; w >>= 1) {
-        if (threadIdx.x < w) {
-            r0[threadIdx.x] += r0[threadIdx.x + w];
-            r1[threadIdx.x] += r1[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = r0[0];
-        out[1] = r1[0];
-        out[2] = (x && *status) ? 1.0 : 0.0;
-        if (host) {
-            host[0] = r0[0];
-            host[1] = r1[0];
-            host[2] = out[2];
-            host[3] = out[3];
-            __threadfence_system();
-        }
     }
 }
 
@@ -1700,7 +1547,7 @@ __device__ void lm_build_done(LmState* st, double chi, double maxdiag) {
 // an iteration's end the next iteration's start is recorded here (ini_chi = the accepted chi2, qmax 0)
 // and its unit builds (phase 0)
 __device__ void lm_trial_done(LmState* st, double chi, double scale_part, bool failed, LmProgress* prog,
-                              bool flip_lin = false, bool fast = false) {
+                              bool fast = false) {
     double tempChi = chi;
     if (failed) tempChi = DBL_MAX;
     double rho = st->current_chi - tempChi;
@@ -1713,7 +1560,6 @@ __device__ void lm_trial_done(LmState* st, double chi, double scale_part, bool f
         st->ni = 2;
         st->current_chi = tempChi;
         st->reject = 0;
-        if (flip_lin) st->lin ^= 1;  // the trial's linearisation (k_u_edges_trial<true>) is the next build's
     } else {
         st->lambda *= st->ni;
         st->ni *= 2;
@@ -1895,113 +1741,15 @@ __global__ __launch_bounds__(64) void k_u_schur(int n, int nf, int nblk, const d
                                                 const int32_t* __restrict__ blk_off, const EdgePair* __restrict__ pairs,
                                                 const int32_t* __restrict__ cnt, const int32_t* __restrict__ pose_off,
                                                 const LandEdge* __restrict__ pose_fl, const double* __restrict__ z,
-                                                const double* __restrict__ hpl, size_t hpl_alt,
+                                                const double* __restrict__ hpl,
                                                 const double* __restrict__ hpp, double* __restrict__ S,
                                                 const double* __restrict__ cb, const double* __restrict__ bp,
                                                 double* __restrict__ bs, const LmState* __restrict__ st, int primary) {
     if (lm_skip(st, kGateTrial)) return;
-    hpl += hpl_cur(st, hpl_alt);
     if ((int)blockIdx.x < nblk)
         ba_schur_block(blockIdx.x, threadIdx.x, n, nf, *lam, primary, blk_off, pairs, cnt, z, hpl, hpp, S);
     else
         ba_schur_rhs(blockIdx.x - nblk, threadIdx.x, pose_off, pose_fl, cb, bp, primary, bs);
-}
-
-// unit step 6 (trial): x_l per landmark and its update, then the pose updates; a rejected previous
-// trial is undone here (from the backup) instead of by a restore launch.  Each block also leaves its
-// part of computeScale, sum x (lambda x + b) over its vertices' rows, in part2[block] (summed in
-// block order by k_u_edges_trial: one load round there instead of a pass over x and b).
-__global__ __launch_bounds__(kT) void k_u_backsub_update(int nl, int nf, int n, const double* __restrict__ lam,
-                                                         const int32_t* __restrict__ off, const int32_t* __restrict__ eidx,
-                                                         const int32_t* __restrict__ erow, const double* __restrict__ hpl,
-                                                         size_t hpl_alt, const double* __restrict__ bl,
-                                                         const double* __restrict__ hll, double* __restrict__ x,
-                                                         const double* __restrict__ bp, const int32_t* __restrict__ free_pose,
-                                                         const int32_t* __restrict__ land_point, double* __restrict__ pose,
-                                                         double* __restrict__ pose_bak, double* __restrict__ point,
-                                                         double* __restrict__ point_bak, double* __restrict__ part2,
-                                                         const LmState* __restrict__ st, int pose_scale) {
-    if (lm_skip(st, kGateTrial)) return;
-    hpl += hpl_cur(st, hpl_alt);
-    const bool rej = st->reject != 0;
-    const double lambda = *lam;
-    const int t = blockIdx.x * kT + threadIdx.x;
-    double c = 0.0;
-    if (t < nl) {
-        double xl[3];
-        ba_backsub(t, n, lambda, off, eidx, erow, hpl, bl, hll, x, xl);
-        for (int r = 0; r < 3; ++r) c += xl[r] * (lambda * xl[r] + bl[3 * (size_t)t + r]);
-        double* X = point + 3 * (size_t)land_point[t];
-        double* Xb = point_bak + 3 * (size_t)land_point[t];
-        for (int i = 0; i < 3; ++i) {
-            const double v = rej ? Xb[i] : X[i];
-            Xb[i] = v;
-            X[i] = v + xl[i];
-        }
-    } else if (t < nl + nf) {
-        const int p = t - nl;
-        double* T = pose + 7 * (size_t)free_pose[p];
-        double* Tb = pose_bak + 7 * (size_t)free_pose[p];
-        double v[7], u[6];
-        for (int i = 0; i < 6; ++i) u[i] = x[6 * (size_t)p + i];
-        if (pose_scale)  // (sharded: the pose rows' computeScale part on rank 0 only)
-            for (int i = 0; i < 6; ++i) c += u[i] * (lambda * u[i] + bp[6 * (size_t)p + i]);
-        for (int i = 0; i < 7; ++i) {
-            v[i] = rej ? Tb[i] : T[i];
-            Tb[i] = v[i];
-        }
-        se3_oplus(v, u);
-        for (int i = 0; i < 7; ++i) T[i] = v[i];
-    }
-    const double bsum = block_sum<kT>(c);
-    if (threadIdx.x == 0) part2[blockIdx.x] = bsum;
-}
-
-// unit step 7 (trial): errors at the new estimate (with kLin also its linearisation: Hll/b_l and
-// Hpp/b_p parts in place -- nothing reads them before the next build -- and Hpl into the other half);
-// the last block sums chi2 and computeScale (part2, from k_u_backsub_update) and runs the trial
-// controller, which on accept makes the kLin linearisation current: the next iteration's build at
-// the same estimate would compute exactly these values
-template <bool kLin>
-__global__ __launch_bounds__(kT) void k_u_edges_trial(int ne, const EdgeDev* __restrict__ edges,
-                                                      const orb_ba_camera_t* __restrict__ cams,
-                                                      const double* __restrict__ pose, const double* __restrict__ point,
-                                                      const int32_t* __restrict__ pose_h, Huber2 hub,
-                                                      double* __restrict__ err, double* __restrict__ rho0_out,
-                                                      double* __restrict__ ecl, double* __restrict__ hpl, size_t hpl_alt,
-                                                      double* __restrict__ ecp, double* __restrict__ part,
-                                                      unsigned* counter, const double* __restrict__ part2, int nparts2,
-                                                      const int32_t* __restrict__ status, double* __restrict__ scal,
-                                                      LmState* st, LmProgress* prog, int dist, double* __restrict__ sc_part,
-                                                      const volatile int32_t* h_stop) {
-    if (lm_skip(st, kGateTrial)) return;
-    const int e = blockIdx.x * kT + threadIdx.x;
-    double r = 0.0;
-    if (e < ne)
-        r = ba_edge<kLin>(e, edges, cams, pose, point, pose_h, hub, err, rho0_out, ecl, hpl + (st->lin ? 0 : hpl_alt),
-                          ecp, 0);
-    const double bsum = block_sum<kT>(r);
-    if (threadIdx.x == 0) part[blockIdx.x] = bsum;
-    if (!last_block(counter)) return;
-    double c = 0.0, d = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += kT) c += part[i];
-    for (int i = threadIdx.x; i < nparts2; i += kT) d += part2[i];
-    const double chi = block_sum<kT>(c);
-    const double scale = block_sum<kT>(d);
-    if (threadIdx.x == 0) {
-        if (dist) {  // this rank's parts and its stop flag, for k_lm_trial_ctl after the all-reduce
-            sc_part[0] = chi;
-            sc_part[1] = scale;
-            sc_part[2] = (h_stop && *h_stop) ? 1.0 : 0.0;
-        } else {
-            const bool failed = *status != 0;
-            scal[0] = chi;
-            scal[1] = scale;
-            scal[2] = failed ? 1.0 : 0.0;
-            lm_trial_done(st, chi, scale, failed, prog, kLin);
-        }
-        *counter = 0;
-    }
 }
 
 // Fast unit (round 6; one process, the single-workgroup Cholesky): steps 1-3 in one landmark-major
@@ -2135,7 +1883,7 @@ __global__ __launch_bounds__(64) void k_u_schur2(int n, int nf, int nblk, const 
     }
 }
 
-// unit steps 6 + 7 in one launch, landmark-major: thread l computes x_l (back-substitution), pushes
+// the trial's last launch (both units), landmark-major: thread l computes x_l (back-substitution), pushes
 // and moves landmark l, and evaluates the errors of the landmark's edges (all of them, in edge order)
 // at the new estimate, with the new point from registers.  A block is two waves: wave 0 takes kT
 // landmarks; wave 1 the poses (pose_mode 1, nf <= kT): every block computes the whole pose update into
@@ -2145,8 +1893,8 @@ __global__ __launch_bounds__(64) void k_u_schur2(int n, int nf, int nblk, const 
 // k_u_pose_update moved them before this launch (and left their computeScale part in *pscale); 0: no
 // free pose.  Per block: the chi2 partial into part[block], the landmarks' computeScale partial into
 // part2[block]; the last block sums both in block order, adds the poses' part (in pose order) and runs
-// the trial controller, as k_u_edges_trial<false> does.  The sums are grouped by landmark instead of
-// by edge block: the same terms, another rounding order.
+// the trial controller (sharded: leaves the sums for k_lm_trial_ctl).  A rejected previous trial is
+// undone here (from the backup) instead of by a restore launch.
 constexpr int kLandEdgeBatch = 8;  // a landmark's edges evaluated 8 at a time (loads issued together; the
                                    // first batch's before the back-substitution)
 constexpr int kLT = 2 * kT;        // k_u_land_trial's block: landmark wave + pose wave
@@ -2154,7 +1902,7 @@ static_assert(kT == 64, "k_u_land_trial: one wave of landmarks, one of poses");
 __global__ __launch_bounds__(kLT) void k_u_land_trial(int nl, int n, const double* __restrict__ lam,
                                                      const int32_t* __restrict__ landf_off, const int32_t* __restrict__ landf_edge,
                                                      const int32_t* __restrict__ landf_row, const double* __restrict__ hpl,
-                                                     size_t hpl_alt, const double* __restrict__ bl,
+                                                     const double* __restrict__ bl,
                                                      const double* __restrict__ hll, double* __restrict__ x,
                                                      const int32_t* __restrict__ land_point, double* __restrict__ point,
                                                      double* __restrict__ point_bak, const int32_t* __restrict__ land_off,
@@ -2169,7 +1917,6 @@ __global__ __launch_bounds__(kLT) void k_u_land_trial(int nl, int n, const doubl
                                                      int fast) {
     if (lm_skip(st, kGateTrial)) return;
     __shared__ double s_new[kT][7], s_base[kT][7], s_pc[kT];
-    hpl += hpl_cur(st, hpl_alt);
     const bool rej = st->reject != 0;
     const double lambda = *lam;
     const int tid = threadIdx.x, pw = tid - kT;  // pw: the pose wave's lane (wave 1)
@@ -2283,7 +2030,7 @@ __global__ __launch_bounds__(kLT) void k_u_land_trial(int nl, int n, const doubl
             scal[0] = chi;
             scal[1] = scale;
             scal[2] = failed ? 1.0 : 0.0;
-            lm_trial_done(st, chi, scale, failed, prog, false, fast != 0);
+            lm_trial_done(st, chi, scale, failed, prog, fast != 0);
         }
         *counter = 0;
     }
@@ -2292,7 +2039,6 @@ __global__ __launch_bounds__(kLT) void k_u_land_trial(int nl, int n, const doubl
 // sharded trial controller, after the all-reduce of the trial partials (sc_red: chi2, computeScale,
 // the number of ranks whose stop flag is raised): every rank takes the same decision; a raised flag
 // on any rank ends the solve after this trial (g2o's force-stop flag, tested between iterations)
-template <bool kLin>
 __global__ __launch_bounds__(64) void k_lm_trial_ctl(const double* __restrict__ sc_red, const int32_t* __restrict__ status,
                                                      double* __restrict__ scal, LmState* st, LmProgress* prog) {
     if (lm_skip(st, kGateTrial)) return;
@@ -2301,7 +2047,7 @@ __global__ __launch_bounds__(64) void k_lm_trial_ctl(const double* __restrict__ 
     scal[0] = sc_red[0];
     scal[1] = sc_red[1];
     scal[2] = failed ? 1.0 : 0.0;
-    lm_trial_done(st, sc_red[0], sc_red[1], failed, prog, kLin);
+    lm_trial_done(st, sc_red[0], sc_red[1], failed, prog);
     if (sc_red[2] > 0 && !st->done) {
         st->done = 1;
         prog->done = 1;
@@ -2328,6 +2074,42 @@ struct DevBuf {
         cap = 0;
     }
 };
+
+// Everything the LM unit's launches read (launch_unit and the launchers it calls take nothing else).
+// A plain struct, cleared with memset before it is filled (padding included), so that its bytes are
+// the captured graph's cache key: an argument added here cannot be left out of the key.
+struct UnitArgs {
+    hipStream_t s;
+    ::orb_ba_s* coll;  // the sharded unit's collectives (dev_reduce2; never captured); null on one process
+    int n, nf, nl, ne, nfe, nblk, NT;
+    int nparts;     // edge blocks: k_u_edges_build's chi2 partials in part[0 .. nparts)
+    int pose_mode;  // k_u_land_trial: 0 no free pose, 1 poses in its LDS (nf <= kT), 2 k_u_pose_update
+    int fast, dist, primary, world, rank, use_rows, rows_lds, units_per_launch;
+    size_t rows_lds_bytes;
+    Huber2 hub;
+    LmState* lm;
+    const double* lam;  // the trial's lambda (in *lm)
+    LmProgress* h_prog;
+    const int32_t* h_stop;
+    const EdgeDev* edges;
+    const orb_ba_camera_t* cams;
+    double *pose, *pose_bak, *point, *point_bak, *err, *rho0, *ecl, *hpl, *ecp, *hpp, *bp, *bl, *hll, *z, *cb, *S, *bs, *x,
+        *scal;
+    double *part, *lt_chi, *lt_scale, *pmax;  // block partials (the layout: ba_upload_structure)
+    unsigned* counters;
+    int32_t* status;
+    const int32_t *pose_h, *free_pose, *land_point, *land_off, *land_edge, *landf_off, *landf_edge, *landf_row, *fland,
+        *pose_off, *blk_off, *blk_cnt;
+    const LandEdge* pose_fl;
+    const EdgePair* pairs;
+    // sharded: this rank's partials p_* and their all-reduced sums r_* ([Hpp | b_p], the build scalars,
+    // [S | b_S], the trial scalars)
+    double *p_hb, *p_scb, *r_hb, *r_scb, *p_sb, *p_sct, *r_sct;
+    double *lpub, *ypub, *racc;  // k_ba_chol_rows
+    unsigned* cflag;
+    int64_t* trace;  // ORBGPU_BA_TRACE: the next single-workgroup Cholesky records its stamps (not captured)
+};
+static_assert(std::is_trivially_copyable<UnitArgs>::value, "UnitArgs is compared and copied as bytes");
 
 }  // namespace
 
@@ -2395,7 +2177,7 @@ struct orb_ba_s {
     orbgpu_ba::BaStructure st;  // the host structure of the last solve (vectors reused)
     hipStream_t stream = nullptr;
     hipStream_t tail = nullptr;  // the end of a device-driven solve, beside the queued no-op unit
-    DevBuf<double> pose, pose_bak, point, point_bak, err, rho0, ecl, hpl, ecp, hpp, hll, b, z, cb, S, bs, x, scal;
+    DevBuf<double> pose, pose_bak, point, point_bak, err, rho0, ecl, hpl, ecp, hpp, hll, z, cb, S, x, scal;
     DevBuf<EdgeDev> edges;
     DevBuf<orb_ba_camera_t> cams;
     DevBuf<int32_t> pose_h, free_pose, land_point, land_off, land_edge, landf_off, landf_edge, landf_row, fland, pose_off,
@@ -2403,10 +2185,9 @@ struct orb_ba_s {
     DevBuf<LandEdge> pose_fl;
     DevBuf<int32_t> blk_off, blk_cnt;  // Schur block product lists (k_ba_schur_pairs)
     DevBuf<EdgePair> pairs;
-    DevBuf<uint8_t> depth;
-    double* h_scal = nullptr;  // pinned: [0] chi2, [1] scale, [2] status, [3] maxdiag, [4] stop, [5] lambda
+    double* h_scal = nullptr;  // pinned: [4] the stop flag, [6] a local failure, as agreed across the ranks
     DevBuf<LmState> lm;        // device-driven LM state
-    DevBuf<double> part;       // per-block chi2 partials of the fused unit kernels
+    DevBuf<double> part;       // per-block partials of the fused unit kernels (ba_upload_structure)
     DevBuf<unsigned> counters;  // last-block counters of the fused unit kernels
     uint8_t* h_stage = nullptr;  // pinned staging of the per-solve inputs
     size_t h_stage_cap = 0;
@@ -2418,11 +2199,11 @@ struct orb_ba_s {
     DevBuf<uint8_t> d_stage;
     LmProgress* h_prog = nullptr;  // pinned, written by k_lm_trial_done
     hipEvent_t unit_ev[2] = {nullptr, nullptr};
-    // the LM unit (7 launches) captured as a HIP graph, reused while its launch arguments are unchanged
+    // the LM units of one graph launch (4 or 6 kernel launches each) captured as a HIP graph, reused while
+    // their launch arguments (unit_key, compared as bytes) are unchanged
     hipGraph_t unit_graph = nullptr;
     hipGraphExec_t unit_exec = nullptr;
-    std::vector<uintptr_t> unit_key;
-    float ms_total = 0;
+    UnitArgs unit_key;
     // multi-GPU: ranks own landmark ranges; partial sums are all-reduced
     int world = 1, rank = 0;
     orb_ba_host_reduce_fn host_fn = nullptr;
@@ -2444,8 +2225,8 @@ struct orb_ba_s {
     DevBuf<unsigned> cflag;
 
     void release() {
-        for (auto* d : {&pose, &pose_bak, &point, &point_bak, &err, &rho0, &ecl, &hpl, &ecp, &hpp, &hll, &b, &z,
-                        &cb, &S, &bs, &x, &scal, &lpub, &ypub, &racc})
+        for (auto* d : {&pose, &pose_bak, &point, &point_bak, &err, &rho0, &ecl, &hpl, &ecp, &hpp, &hll, &z,
+                        &cb, &S, &x, &scal, &lpub, &ypub, &racc})
             d->release();
         cflag.release();
         edges.release();
@@ -2458,22 +2239,10 @@ struct orb_ba_s {
         blk_off.release();
         blk_cnt.release();
         pairs.release();
-        depth.release();
     }
 };
 
 namespace {
-
-template <typename T>
-bool upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t s) {
-    if (!d.grow(n)) return false;
-    return n == 0 || hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, s) == hipSuccess;
-}
-
-template <typename T>
-bool upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t s) {
-    return upload(d, h.data(), h.size(), s);
-}
 
 unsigned grid(size_t n, int t = kT) { return (unsigned)std::max<size_t>(1, (n + t - 1) / t); }
 
@@ -2685,10 +2454,6 @@ int orb_ba_dist_init_host(orb_ba_t h, orb_ba_host_reduce_fn fn, void* ctx, int w
     return ORB_OK;
 }
 
-static bool stop_requested(const orb_ba_options_t* opt) {
-    return (opt->stop_flag && *opt->stop_flag) || (opt->stop_flag_bool && *opt->stop_flag_bool);
-}
-
 // Debug hook (not in the public header): force_rows selects k_ba_chol_rows for every n; row >= 0 arms
 // the forced timeout of that tile row's first wait in the next k_ba_chol_rows launch.  Synchronous.
 int orb_debug_ba_chol_timeout(int force_rows, int row) {
@@ -2711,159 +2476,344 @@ int orb_debug_ba_chol_timeout_status(int32_t* status) {
     return ORB_OK;
 }
 
-int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* opt, double* edge_chi2,
-                    uint8_t* edge_depth_ok, orb_ba_result_t* res) {
-    if (!h || !pr || !opt || !res) return orbgpu_fail(ORB_ERR_ARG, "null BA argument");
-    memset(res, 0, sizeof(*res));
-    // ORBGPU_BA_TRACE: host-side phase times of each solve on stderr (structure, upload+LM, results)
-    static const bool trace = getenv("ORBGPU_BA_TRACE") != nullptr;
-    using clk = std::chrono::steady_clock;
-    const clk::time_point t_in = clk::now();
-    clk::time_point t_struct = t_in, t_solve = t_in, t_order = t_in, t_csr = t_in, t_pairs = t_in, t_pack = t_in;
-    double unit_t[32];  // (trace) when each unit launch was seen complete, from t_pack
+// ---- the LM unit's launches (everything they read is in UnitArgs) ----------------------------------
+namespace {
+
+// ORBGPU_BA_TRACE: host-side phase times of each solve on stderr (structure, upload+LM, results), and
+// the first single-workgroup Cholesky of the process records its phase stamps (dump_chol_trace)
+bool ba_trace_on() {
+    static const bool on = getenv("ORBGPU_BA_TRACE") != nullptr;
+    return on;
+}
+int* chol_trace_left() {
+    static int left = ba_trace_on() ? 1 : 0;
+    return &left;
+}
+
+// unit step 1 (6-launch unit; the fast unit once, before its first unit)
+void launch_edges_build(const UnitArgs& a) {
+    hipLaunchKernelGGL(k_u_edges_build, dim3(a.nparts), dim3(kT), 0, a.s, a.ne, a.edges, a.cams, a.pose, a.point,
+                       a.pose_h, a.hub, a.err, a.rho0, a.ecl, a.hpl, a.ecp, a.part, (const LmState*)a.lm);
+}
+
+// unit step 2 (as above).  Sharded: into this rank's partials.
+void launch_reduce_build(const UnitArgs& a) {
+    hipLaunchKernelGGL(k_u_reduce_build, dim3(a.nf + grid(a.nl, 64)), dim3(64), 0, a.s, a.nf, a.nl, a.pose_off,
+                       a.pose_fl, a.ecp, a.dist ? a.p_hb : a.hpp, a.dist ? a.p_hb + 36 * (size_t)a.nf : a.bp,
+                       a.land_off, a.land_edge, a.ecl, a.hll, a.bl, a.part, a.nparts, a.counters, a.scal, a.lm,
+                       a.dist ? 1 : 0, a.p_scb, a.rank, a.pmax);
+}
+
+// Cholesky + solves of the reduced camera system [S | b_S] -> x; with the tile-row kernel, pt.pose set:
+// k_u_pose_update behind it.  hpp_add / lam_add: the fast unit's Hpp + lambda I (k_ba_chol_mf2).
+void launch_chol(const UnitArgs& a, const PoseTail& pt, const double* hpp_add = nullptr,
+                 const double* lam_add = nullptr) {
+    const LmState* g = a.lm;
+    if (a.use_rows) {
+        if (a.rows_lds)
+            hipLaunchKernelGGL(k_ba_chol_rows<true>, dim3(a.NT), dim3(kRowThreads), a.rows_lds_bytes, a.s, a.n, a.S,
+                               a.bs, a.x, a.status, a.lpub, a.ypub, a.cflag, a.racc, g);
+        else
+            hipLaunchKernelGGL(k_ba_chol_rows<false>, dim3(a.NT), dim3(kRowThreads), a.rows_lds_bytes, a.s, a.n, a.S,
+                               a.bs, a.x, a.status, a.lpub, a.ypub, a.cflag, a.racc, g);
+        if (pt.pose) hipLaunchKernelGGL(k_u_pose_update, dim3(1), dim3(256), 0, a.s, pt, (const double*)a.x, g);
+        return;
+    }
+    int64_t* tr = nullptr;
+    if (a.trace && *chol_trace_left()) {
+        hipMemsetAsync(a.trace, 0, kTraceLen * sizeof(int64_t), a.s);
+        tr = a.trace;
+    }
+    hipLaunchKernelGGL((k_ba_chol_mf2<kMf2TileWaves>), dim3(1), dim3((kMf2TileWaves + 1) * 64), kMf2Lds, a.s, a.n,
+                       a.S, a.bs, a.x, a.status, tr, g, hpp_add, lam_add);
+    if (tr) {
+        *chol_trace_left() = 0;
+        dump_chol_trace(tr, a.n, a.s);
+    }
+}
+
+// the trial's last launch (both units)
+void launch_land_trial(const UnitArgs& a, const PoseTail& pt) {
+    hipLaunchKernelGGL(k_u_land_trial, dim3(grid(a.nl)), dim3(kLT), 0, a.s, a.nl, a.n, a.lam, a.landf_off,
+                       a.landf_edge, a.landf_row, a.hpl, a.bl, a.hll, a.x, a.land_point, a.point, a.point_bak,
+                       a.land_off, a.land_edge, a.edges, a.cams, a.pose, a.pose_h, pt, a.pose_mode, a.hub, a.err,
+                       a.rho0, a.lt_chi, a.lt_scale, a.counters + 1, a.status, a.scal, a.lm, a.h_prog,
+                       a.dist ? 1 : 0, a.p_sct, (const volatile int32_t*)a.h_stop, a.fast);
+}
+
+// One unit = one LM trial: the build's part (gated to the start of an iteration), the trial, the trial
+// controller.  Every unit launches the same kernels with the same arguments; the device state gates
+// them, and once the solve is done a unit is a run of no-op launches.
+//   The fast unit (one process, the single-workgroup Cholesky), 4 launches: k_u_land_build
+// (linearisation, Hll / b_l, Z and cb), k_u_schur2 (S without its diagonal Hpp + lambda I, b_S, Hpp /
+// b_p), the Cholesky (adding Hpp + lambda I as it loads S), k_u_land_trial.  The solve's first build
+// (lambda from max diag) runs once before the units, with the build controller (ba_prepare_units).
+//   The 6-launch unit: reductions (+ chi2, max diag, build controller), Schur edges, Schur blocks +
+// rhs, Cholesky + solves (beyond kT free poses k_u_pose_update moves the poses behind it),
+// k_u_land_trial.  Sharded, its all-reduces are stream-ordered between the launches (every rank
+// reduces to the same values and takes the same LM decisions); coll_ok: no collective has failed.
+void launch_unit(const UnitArgs& a, bool& coll_ok) {
+    const hipStream_t s = a.s;
+    const double* lam = a.lam;
+    const LmState* L = a.lm;
+    const PoseTail pt_unit = PoseTail{a.free_pose, a.pose, a.pose_bak, a.bp, lam, a.scal + 8, a.nf, a.primary};
+    if (a.fast) {
+        hipLaunchKernelGGL(k_u_land_build, dim3(grid((size_t)a.nl * kLB)), dim3(kT), 0, s, a.nl, lam, a.land_off,
+                           a.land_edge, a.edges, a.cams, a.pose, a.point, a.pose_h, a.hub, a.err, a.rho0, a.hpl, a.ecp,
+                           a.hll, a.bl, a.z, a.cb, L);
+        if (a.nf) {
+            hipLaunchKernelGGL(k_u_schur2, dim3(a.nblk + 2 * a.nf), dim3(64), 0, s, a.n, a.nf, a.nblk, lam, a.blk_off,
+                               a.pairs, a.blk_cnt, a.pose_off, a.pose_fl, a.z, a.hpl, a.ecp, a.hpp, a.bp, a.S, a.cb,
+                               a.bs, L);
+            launch_chol(a, PoseTail{}, a.hpp, lam);
+        }
+        launch_land_trial(a, pt_unit);
+        return;
+    }
+    launch_edges_build(a);
+    launch_reduce_build(a);
+    if (a.dist) {  // one collective for [Hpp | b_p | build scalars], then the sums into place
+        const size_t nhb = 36 * (size_t)a.nf + a.n, nsb = 4 + a.world;
+        coll_ok = coll_ok && dev_reduce2(a.coll, a.p_hb, a.r_hb, nhb + nsb, ORB_BA_SUM) &&
+                  hipMemcpyAsync(a.hpp, a.r_hb, nhb * sizeof(double), hipMemcpyDeviceToDevice, s) == hipSuccess;
+        hipLaunchKernelGGL(k_lm_build_ctl, dim3(1), dim3(64), 0, s, a.nf, (const double*)a.hpp, (const double*)a.r_scb,
+                           a.world, a.scal, a.lm);
+    }
+    if (a.nfe)
+        hipLaunchKernelGGL(k_ba_schur_edges, dim3(grid(a.nfe)), dim3(kT), 0, s, a.nfe, lam, a.landf_edge, a.fland,
+                           a.hll, a.bl, a.hpl, a.z, a.cb, L);
+    if (a.nf) {
+        hipLaunchKernelGGL(k_u_schur, dim3(a.nblk + a.nf), dim3(64), 0, s, a.n, a.nf, a.nblk, lam, a.blk_off, a.pairs,
+                           a.blk_cnt, a.pose_off, a.pose_fl, a.z, a.hpl, a.hpp, a.dist ? a.p_sb : a.S, a.cb, a.bp,
+                           a.dist ? a.p_sb + (size_t)a.n * a.n : a.bs, L, a.primary);
+        if (a.dist) coll_ok = coll_ok && dev_reduce2(a.coll, a.p_sb, a.S, (size_t)a.n * a.n + a.n, ORB_BA_SUM);
+        launch_chol(a, a.pose_mode == 2 ? pt_unit : PoseTail{});
+    }
+    launch_land_trial(a, pt_unit);
+    if (a.dist) {
+        coll_ok = coll_ok && dev_reduce2(a.coll, a.p_sct, a.r_sct, 4, ORB_BA_SUM);
+        hipLaunchKernelGGL(k_lm_trial_ctl, dim3(1), dim3(64), 0, s, (const double*)a.r_sct, (const int32_t*)a.status,
+                           a.scal, a.lm, a.h_prog);
+    }
+}
+
+// undo a rejected last trial (gated on the device state)
+void launch_restore(const UnitArgs& a, hipStream_t rs) {
+    hipLaunchKernelGGL(k_ba_restore, dim3(grid(a.nf + a.nl)), dim3(kT), 0, rs, a.nf, a.nl, a.free_pose, a.land_point,
+                       a.pose, a.pose_bak, a.point, a.point_bak, (const LmState*)a.lm);
+}
+
+// ---- one solve, in stages --------------------------------------------------------------------------
+using clk = std::chrono::steady_clock;
+double us_between(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+
+// The state of one orb_ba_optimize call, handed through its stages in order.  A stage returns false to
+// end the call with `rc`.
+struct BaSolve {
+    orb_ba_s* h;
+    orb_ba_problem_t* pr;
+    const orb_ba_options_t* opt;
+    double* edge_chi2;
+    uint8_t* edge_depth_ok;
+    orb_ba_result_t* res;
+    int rc = ORB_OK;
+    int np = 0, nq = 0, ne_all = 0;
+    bool dist = false, primary = true;
+    bool early = false;  // one rank: the raw inputs went up before the structure was built
+    hipStream_t s = nullptr;
+    hipStream_t rs = nullptr;  // the stream of the restore and the results (ba_drive)
+    std::vector<double> pose;  // the poses, normalised
+    size_t ne1 = 1;            // max(this rank's edges, 1)
+    UnitArgs u;                // cleared by orb_ba_optimize, filled by the stages
+    bool use_graph = false;
+    // ORBGPU_BA_TRACE
+    clk::time_point t_in, t_struct, t_solve, t_order, t_csr, t_pairs, t_pack;
+    double unit_t[32];  // when each unit launch was seen complete, from t_pack
     int n_unit_t = 0;
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    const int np = pr->n_poses, nq = pr->n_points, ne_all = pr->n_edges;
+};
+
+bool ba_fail(BaSolve& c, int code, const char* msg) {
+    c.rc = orbgpu_fail(code, msg);
+    return false;
+}
+
+bool stop_requested(const orb_ba_options_t* opt) {
+    return (opt->stop_flag && *opt->stop_flag) || (opt->stop_flag_bool && *opt->stop_flag_bool);
+}
+
+// the stop flag, agreed across the ranks (MAX) so that every rank takes the same path
+bool ba_stop(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    const double f = stop_requested(c.opt) ? 1.0 : 0.0;
+    if (!c.dist) return f != 0.0;
+    h->h_scal[4] = f;
+    hipMemcpyAsync(h->scal.p + 4, &h->h_scal[4], sizeof(double), hipMemcpyHostToDevice, c.s);
+    dev_reduce(h, h->scal.p + 4, 1, ORB_BA_MAX);
+    hipMemcpyAsync(&h->h_scal[4], h->scal.p + 4, sizeof(double), hipMemcpyDeviceToHost, c.s);
+    hipStreamSynchronize(c.s);
+    return h->h_scal[4] != 0.0;
+}
+
+// A local failure before the solve must be agreed by every rank (MAX over the ranks), so that no
+// rank returns while the others block in the next collective.  Single process: the local value.
+bool ba_agree_fail(BaSolve& c, bool local_fail) {
+    orb_ba_s* h = c.h;
+    if (!c.dist) return local_fail;
+    h->h_scal[6] = local_fail ? 1.0 : 0.0;
+    hipMemcpyAsync(h->scal.p + 6, &h->h_scal[6], sizeof(double), hipMemcpyHostToDevice, c.s);
+    const bool ok = dev_reduce(h, h->scal.p + 6, 1, ORB_BA_MAX);
+    hipMemcpyAsync(&h->h_scal[6], h->scal.p + 6, sizeof(double), hipMemcpyDeviceToHost, c.s);
+    if (hipStreamSynchronize(c.s) != hipSuccess || !ok) return true;
+    return h->h_scal[6] != 0.0;
+}
+
+// [items table | data] of a Stager in one pinned buffer, one copy, one scatter launch
+bool ba_upload_stage(hipStream_t s, const Stager& sg, uint8_t*& hbuf, size_t& hcap, DevBuf<uint8_t>& dbuf) {
+    if (sg.items.empty()) return true;
+    const size_t data_off = sg.table_bytes(), total = data_off + sg.data_bytes;
+    if (total > hcap) {
+        if (hbuf) hipHostFree(hbuf);
+        hbuf = nullptr;
+        hcap = 0;
+        if (hipHostMalloc(&hbuf, total, hipHostMallocDefault) != hipSuccess) return false;
+        hcap = total;
+    }
+    if (!dbuf.grow(total)) return false;
+    sg.pack(hbuf);
+    if (hipMemcpyAsync(dbuf.p, hbuf, total, hipMemcpyHostToDevice, s) != hipSuccess) return false;
+    size_t maxb = 0;
+    for (const ScatterItem& it : sg.items) maxb = std::max<size_t>(maxb, it.bytes);
+    const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (maxb / 16 + 255) / 256));
+    hipLaunchKernelGGL(k_ba_scatter, dim3(gx, (unsigned)sg.items.size()), dim3(256), 0, s, dbuf.p + data_off,
+                       (const ScatterItem*)dbuf.p);
+    return hipGetLastError() == hipSuccess;
+}
+
+// stage 1: the arguments
+bool ba_validate(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    const orb_ba_problem_t* pr = c.pr;
+    const int np = c.np = pr->n_poses, nq = c.nq = pr->n_points, ne_all = c.ne_all = pr->n_edges;
     if (np < 0 || nq < 0 || ne_all < 0 || (np && (!pr->pose || !pr->pose_id || !pr->pose_fixed || !pr->pose_camera)) ||
-        (nq && (!pr->point || !pr->point_id)) || (ne_all && !pr->edges) || opt->iterations < 0)
-        return orbgpu_fail(ORB_ERR_ARG, "invalid BA problem");
+        (nq && (!pr->point || !pr->point_id)) || (ne_all && !pr->edges) || c.opt->iterations < 0)
+        return ba_fail(c, ORB_ERR_ARG, "invalid BA problem");
     for (int e = 0; e < ne_all; ++e) {
         const orb_ba_edge_t& E = pr->edges[e];
         if (E.point < 0 || E.point >= nq || E.pose < 0 || E.pose >= np || (E.stereo != 0 && E.stereo != 1))
-            return orbgpu_fail(ORB_ERR_ARG, "BA edge references a missing vertex");
+            return ba_fail(c, ORB_ERR_ARG, "BA edge references a missing vertex");
     }
-    const bool dist = h->world > 1 || h->force_dist;
-    const bool primary = h->rank == 0;
-    hipStream_t s = h->stream;
-    if (!h->scal.grow(16)) return orbgpu_fail(ORB_ERR_DEVICE, "BA scalar buffer");
-    // the stop flag, agreed across the ranks (MAX) so that every rank takes the same path
-    auto stop = [&]() -> bool {
-        double f = stop_requested(opt) ? 1.0 : 0.0;
-        if (!dist) return f != 0.0;
-        h->h_scal[4] = f;
-        hipMemcpyAsync(h->scal.p + 4, &h->h_scal[4], sizeof(double), hipMemcpyHostToDevice, s);
-        dev_reduce(h, h->scal.p + 4, 1, ORB_BA_MAX);
-        hipMemcpyAsync(&h->h_scal[4], h->scal.p + 4, sizeof(double), hipMemcpyDeviceToHost, s);
-        hipStreamSynchronize(s);
-        return h->h_scal[4] != 0.0;
-    };
+    c.dist = h->world > 1 || h->force_dist;
+    c.primary = h->rank == 0;
+    c.s = c.rs = h->stream;
+    if (!h->scal.grow(16)) return ba_fail(c, ORB_ERR_DEVICE, "BA scalar buffer");
+    return true;
+}
 
-    // A local failure before the solve must be agreed by every rank (MAX over the ranks), so that no
-    // rank returns while the others block in the next collective.  Single process: the local value.
-    auto agree_fail = [&](bool local_fail) -> bool {
-        if (!dist) return local_fail;
-        h->h_scal[6] = local_fail ? 1.0 : 0.0;
-        hipMemcpyAsync(h->scal.p + 6, &h->h_scal[6], sizeof(double), hipMemcpyHostToDevice, s);
-        const bool ok = dev_reduce(h, h->scal.p + 6, 1, ORB_BA_MAX);
-        hipMemcpyAsync(&h->h_scal[6], h->scal.p + 6, sizeof(double), hipMemcpyDeviceToHost, s);
-        if (hipStreamSynchronize(s) != hipSuccess || !ok) return true;
-        return h->h_scal[6] != 0.0;
-    };
-
-    // [items table | data] of a Stager in one pinned buffer, one copy, one scatter launch
-    auto upload_stage = [&](const Stager& sg, uint8_t*& hbuf, size_t& hcap, DevBuf<uint8_t>& dbuf) -> bool {
-        if (sg.items.empty()) return true;
-        const size_t data_off = sg.table_bytes(), total = data_off + sg.data_bytes;
-        if (total > hcap) {
-            if (hbuf) hipHostFree(hbuf);
-            hbuf = nullptr;
-            hcap = 0;
-            if (hipHostMalloc(&hbuf, total, hipHostMallocDefault) != hipSuccess) return false;
-            hcap = total;
-        }
-        if (!dbuf.grow(total)) return false;
-        sg.pack(hbuf);
-        if (hipMemcpyAsync(dbuf.p, hbuf, total, hipMemcpyHostToDevice, s) != hipSuccess) return false;
-        size_t maxb = 0;
-        for (const ScatterItem& it : sg.items) maxb = std::max<size_t>(maxb, it.bytes);
-        const unsigned gx = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (maxb / 16 + 255) / 256));
-        hipLaunchKernelGGL(k_ba_scatter, dim3(gx, (unsigned)sg.items.size()), dim3(256), 0, s, dbuf.p + data_off,
-                           (const ScatterItem*)dbuf.p);
-        return hipGetLastError() == hipSuccess;
-    };
-    // poses normalised as SE3Quat(q, t) does
-    std::vector<double> pose(pr->pose, pr->pose + 7 * (size_t)np);
-    for (int i = 0; i < np; ++i) {
-        double* q = &pose[7 * (size_t)i + 3];
+// stage 2: poses normalised as SE3Quat(q, t) does.  One rank uses the problem's edges in place: the raw
+// inputs (poses, points, edges, cameras) go up now, and the copy runs while the host builds the
+// structure (it does not need them on the device).  Sharded solves upload their rank's edge copy with
+// the structure.
+bool ba_upload_raw(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    const orb_ba_problem_t* pr = c.pr;
+    c.pose.assign(pr->pose, pr->pose + 7 * (size_t)c.np);
+    for (int i = 0; i < c.np; ++i) {
+        double* q = &c.pose[7 * (size_t)i + 3];
         if (q[3] < 0) for (int k = 0; k < 4; ++k) q[k] = -q[k];
         const double nn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
         if (nn > 0) for (int k = 0; k < 4; ++k) q[k] /= nn;
     }
-    // One rank uses the problem's edges in place: the raw inputs (poses, points, edges, cameras) go up
-    // now, and the copy runs while the host builds the structure below (it does not need them on the
-    // device).  Sharded solves upload their rank's edge copy with the structure.
-    const bool early = !dist && ne_all > 0;
-    if (early) {
+    c.early = !c.dist && c.ne_all > 0;
+    if (c.early) {
         Stager s0;
-        const bool ok0 = s0.add(h->pose, pose) && s0.add(h->point, pr->point, 3 * (size_t)nq) &&
-                         s0.add(h->edges, reinterpret_cast<const EdgeDev*>(pr->edges), (size_t)ne_all) &&
-                         s0.add(h->cams, pr->pose_camera, np) &&
-                         upload_stage(s0, h->h_stage0, h->h_stage0_cap, h->d_stage0);
-        if (!ok0) return orbgpu_fail(ORB_ERR_DEVICE, "BA device allocation / upload");
+        const bool ok0 = s0.add(h->pose, c.pose) && s0.add(h->point, pr->point, 3 * (size_t)c.nq) &&
+                         s0.add(h->edges, reinterpret_cast<const EdgeDev*>(pr->edges), (size_t)c.ne_all) &&
+                         s0.add(h->cams, pr->pose_camera, c.np) &&
+                         ba_upload_stage(c.s, s0, h->h_stage0, h->h_stage0_cap, h->d_stage0);
+        if (!ok0) return ba_fail(c, ORB_ERR_DEVICE, "BA device allocation / upload");
     }
+    return true;
+}
 
-    // ---- structure (initializeOptimization + BlockSolver::buildStructure), csrc/ba_structure.h
+// stage 3a: the structure (initializeOptimization + BlockSolver::buildStructure), csrc/ba_structure.h
+bool ba_structure(BaSolve& c) {
+    orb_ba_s* h = c.h;
     orbgpu_ba::BaStructure& T = h->st;
-    if (!orbgpu_ba::ba_build_structure(pr, h->world, h->rank, T)) {  // SparseOptimizer::optimize returns -1: nothing to do
-        if (early) (void)hipStreamSynchronize(s);  // the raw upload reads the pinned staging the next call rewrites
-        for (int e = 0; e < ne_all; ++e) {
-            if (edge_chi2) edge_chi2[e] = 0;
-            if (edge_depth_ok) edge_depth_ok[e] = 0;
+    if (!orbgpu_ba::ba_build_structure(c.pr, h->world, h->rank, T)) {  // SparseOptimizer::optimize returns -1: nothing to do
+        if (c.early) (void)hipStreamSynchronize(c.s);  // the raw upload reads the pinned staging the next call rewrites
+        for (int e = 0; e < c.ne_all; ++e) {
+            if (c.edge_chi2) c.edge_chi2[e] = 0;
+            if (c.edge_depth_ok) c.edge_depth_ok[e] = 0;
         }
-        return ORB_OK;
+        c.rc = ORB_OK;
+        return false;
     }
-    t_order = t_csr = clk::now();
-    if (stop()) {
-        if (early) (void)hipStreamSynchronize(s);
-        res->stopped = 1;
-        return ORB_ERR_ABORTED;
+    c.t_order = c.t_csr = clk::now();
+    if (ba_stop(c)) {
+        if (c.early) (void)hipStreamSynchronize(c.s);
+        c.res->stopped = 1;
+        c.rc = ORB_ERR_ABORTED;
+        return false;
     }
-    if (agree_fail(T.dup_edge) || agree_fail(T.n_products > INT32_MAX)) {
-        if (early) (void)hipStreamSynchronize(s);
-        return orbgpu_fail(ORB_ERR_ARG, T.dup_edge ? "two edges between one keyframe and one map point"
-                                                   : "BA window too large");
+    if (ba_agree_fail(c, T.dup_edge) || ba_agree_fail(c, T.n_products > INT32_MAX)) {
+        if (c.early) (void)hipStreamSynchronize(c.s);
+        return ba_fail(c, ORB_ERR_ARG, T.dup_edge ? "two edges between one keyframe and one map point"
+                                                  : "BA window too large");
     }
+    c.t_pairs = clk::now();
+    return true;
+}
+
+// stage 3b: the solve's buffers, the structure and the LM state's start in one staging upload, the Schur
+// blocks' product lists, the pinned result buffer; the buffers' addresses into the unit's arguments
+bool ba_upload_structure(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    const orb_ba_problem_t* pr = c.pr;
+    const orbgpu_ba::BaStructure& T = h->st;
+    UnitArgs& u = c.u;
     static_assert(sizeof(EdgeDev) == sizeof(orb_ba_edge_t), "EdgeDev mirrors orb_ba_edge_t");
     const EdgeDev* ledges = reinterpret_cast<const EdgeDev*>(T.ledges);
-    const int nf = T.nf, ne = T.ne, nl = T.nl, nfe = T.nfe, nblk = T.nblk;
+    const int np = c.np, nq = c.nq;
+    const int nf = T.nf, ne = T.ne, nl = T.nl, nblk = T.nblk;
     const int n = 6 * nf, m = 3 * nl;
-    const std::vector<int32_t>& point_l = T.point_l;
-    const std::vector<int32_t>& qdeg = T.qdeg;
-    const std::vector<int32_t>& lmap = T.lmap;
-    t_pairs = clk::now();
 
-    const double tau = 1e-5;
     LmState lm_init{};  // the device-driven loop's start (g2o's Levenberg state before iteration 0)
     lm_init.ni = 2;
-    lm_init.user_lambda = opt->user_lambda_init;
-    lm_init.tau = tau;
-    lm_init.iterations = opt->iterations;
-    lm_init.done = opt->iterations <= 0;
+    lm_init.user_lambda = c.opt->user_lambda_init;
+    lm_init.tau = 1e-5;
+    lm_init.iterations = c.opt->iterations;
+    lm_init.done = c.opt->iterations <= 0;
 
-    t_struct = clk::now();
-    const size_t ne1 = std::max(ne, 1);
+    c.t_struct = clk::now();
+    const size_t ne1 = c.ne1 = std::max(ne, 1);
+    // h->part, the unit kernels' per-block partials: [k_u_edges_build's chi2, one per edge block |
+    // k_u_land_trial's chi2, one per landmark block | its computeScale parts, the same number |
+    // k_u_reduce_build's max |diag|, one per block of its grid (nf + 64-landmark blocks)]
+    const size_t np_edges = grid(ne), np_land = grid(nl), np_max = nf + grid(nl, 64);
     Stager st;
-    bool ok = (early || (st.add(h->pose, pose) && st.add(h->point, pr->point, 3 * (size_t)nq) &&
-                         st.add(h->edges, ledges, (size_t)ne) && st.add(h->cams, pr->pose_camera, np))) &&
-              h->pose_bak.grow(7 * (size_t)np) && h->point_bak.grow(3 * (size_t)nq) && st.add(h->pose_h, T.pose_h) && st.add(h->free_pose, T.free_pose) && st.add(h->land_point, T.land_point) &&
+    bool ok = (c.early || (st.add(h->pose, c.pose) && st.add(h->point, pr->point, 3 * (size_t)nq) &&
+                           st.add(h->edges, ledges, (size_t)ne) && st.add(h->cams, pr->pose_camera, np))) &&
+              h->pose_bak.grow(7 * (size_t)np) && h->point_bak.grow(3 * (size_t)nq) && st.add(h->pose_h, T.pose_h) &&
+              st.add(h->free_pose, T.free_pose) && st.add(h->land_point, T.land_point) &&
               st.add(h->land_off, T.land_off) && st.add(h->land_edge, T.land_edge) &&
               st.add(h->landf_off, T.landf_off) && st.add(h->landf_edge, T.landf_edge) && st.add(h->fland, T.fland) &&
               st.add(h->landf_row, T.landf_row) && st.add(h->pose_off, T.pose_off) && st.add(h->pose_fl, T.pose_fl) &&
               st.add(h->blk_off, T.blk_off) && h->blk_cnt.grow(std::max(nblk, 1)) &&
               h->pairs.grow(std::max<size_t>(1, (size_t)T.blk_off[nblk])) &&
-              h->err.grow(3 * ne1) && h->rho0.grow(ne1) && h->ecl.grow(12 * ne1) && h->hpl.grow(36 * ne1) &&
+              // per edge: the error (3), Hll | b_l parts (9 + 3), Hpl (6 x 3, ba_edge), Hpp | b_p parts (36 + 6)
+              h->err.grow(3 * ne1) && h->rho0.grow(ne1) && h->ecl.grow(12 * ne1) && h->hpl.grow(18 * ne1) &&
               h->ecp.grow(42 * ne1) && h->hpp.grow(36 * (size_t)nf + n + m) && h->hll.grow(9 * (size_t)nl) &&
               h->z.grow(18 * ne1) && h->cb.grow(6 * ne1) && h->S.grow((size_t)n * n + n) &&
-              h->depth.grow(ne1) && h->part.grow(grid(ne) + grid(nl + nf) + nf + grid(nl, 64)) &&
+              h->part.grow(np_edges + 2 * np_land + np_max) &&
               // cleared by the scatter launch: g2o's _x starts zeroed, the scalars, the factorisation
               // status, the last-block counters of the unit kernels; and the device LM state's start
               st.zero(h->x, n + m) && st.zero(h->scal, 8) && st.zero(h->status, 1) && st.zero(h->counters, 2) &&
               st.add(h->lm, &lm_init, 1);
     if (ok && !st.items.empty()) {
-        ok = upload_stage(st, h->h_stage, h->h_stage_cap, h->d_stage);
-        t_pack = clk::now();
+        ok = ba_upload_stage(c.s, st, h->h_stage, h->h_stage_cap, h->d_stage);
+        c.t_pack = clk::now();
         if (ok && nblk)  // the Schur blocks' product lists, for every trial of the solve
-            hipLaunchKernelGGL(k_ba_schur_pairs, dim3(nblk), dim3(64), 0, s, nf, h->pose_off.p, h->pose_fl.p,
+            hipLaunchKernelGGL(k_ba_schur_pairs, dim3(nblk), dim3(64), 0, c.s, nf, h->pose_off.p, h->pose_fl.p,
                                h->blk_off.p, h->pairs.p, h->blk_cnt.p);
     }
     // the pinned result buffer too, before the solve: [poses | points | edge chi2 | depth flags]
@@ -2875,39 +2825,105 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
         ok = hipHostMalloc(&h->h_dl, dl_bytes, hipHostMallocDefault) == hipSuccess;
         if (ok) h->h_dl_cap = dl_bytes;
     }
-    if (agree_fail(!ok)) return orbgpu_fail(ORB_ERR_DEVICE, "BA device allocation / upload");
+    if (ba_agree_fail(c, !ok)) return ba_fail(c, ORB_ERR_DEVICE, "BA device allocation / upload");
+
+    u.s = c.s;
+    u.n = n;
+    u.nf = nf;
+    u.nl = nl;
+    u.ne = ne;
+    u.nfe = T.nfe;
+    u.nblk = nblk;
+    u.NT = (n + 15) / 16;
+    u.nparts = (int)np_edges;
+    u.pose_mode = nf == 0 ? 0 : nf <= kT ? 1 : 2;
+    u.dist = c.dist ? 1 : 0;
+    u.primary = c.primary ? 1 : 0;
+    u.world = h->world;
+    u.rank = h->rank;
+    const float dm = (float)std::sqrt(5.991), ds = (float)std::sqrt(7.815);  // src/Optimizer.cc:1957-1958
+    u.hub = Huber2{(double)dm, (double)ds, (float)((double)dm * (double)dm), (float)((double)ds * (double)ds)};
+    u.lm = h->lm.p;
+    u.lam = &h->lm.p->lambda;
+    u.h_prog = h->h_prog;
+    u.h_stop = h->h_stop;
+    u.edges = h->edges.p;
+    u.cams = h->cams.p;
+    u.pose = h->pose.p;
+    u.pose_bak = h->pose_bak.p;
+    u.point = h->point.p;
+    u.point_bak = h->point_bak.p;
+    u.err = h->err.p;
+    u.rho0 = h->rho0.p;
+    u.ecl = h->ecl.p;
+    u.hpl = h->hpl.p;
+    u.ecp = h->ecp.p;
     // [Hpp | b_p | b_l] and [S | b_S] are contiguous: a sharded solve all-reduces [Hpp | b_p] and
     // [S | b_S] in one collective each
-    double* const HPP = h->hpp.p;
-    double* const BV = HPP + 36 * (size_t)nf;
-    double* const SS = h->S.p;
-    double* const BSV = SS + (size_t)n * n;
+    u.hpp = h->hpp.p;
+    u.bp = u.hpp + 36 * (size_t)nf;
+    u.bl = u.bp + n;
+    u.hll = h->hll.p;
+    u.z = h->z.p;
+    u.cb = h->cb.p;
+    u.S = h->S.p;
+    u.bs = u.S + (size_t)n * n;
+    u.x = h->x.p;
+    u.scal = h->scal.p;
+    u.part = h->part.p;
+    u.lt_chi = u.part + np_edges;
+    u.lt_scale = u.lt_chi + np_land;
+    u.pmax = u.lt_scale + np_land;
+    u.counters = h->counters.p;
+    u.status = h->status.p;
+    u.pose_h = h->pose_h.p;
+    u.free_pose = h->free_pose.p;
+    u.land_point = h->land_point.p;
+    u.land_off = h->land_off.p;
+    u.land_edge = h->land_edge.p;
+    u.landf_off = h->landf_off.p;
+    u.landf_edge = h->landf_edge.p;
+    u.landf_row = h->landf_row.p;
+    u.fland = h->fland.p;
+    u.pose_off = h->pose_off.p;
+    u.blk_off = h->blk_off.p;
+    u.blk_cnt = h->blk_cnt.p;
+    u.pose_fl = h->pose_fl.p;
+    u.pairs = h->pairs.p;
+    return true;
+}
 
-    const float dm = (float)std::sqrt(5.991), ds = (float)std::sqrt(7.815);  // src/Optimizer.cc:1957-1958
-    const Huber2 hub{(double)dm, (double)ds, (float)((double)dm * (double)dm), (float)((double)ds * (double)ds)};
-    // Cholesky + solves of the reduced camera system: the register-resident single-workgroup kernel
-    // (k_ba_chol_mf2) for n <= 16 x kMfMaxNT = 288, the tile-row kernel (k_ba_chol_rows, one workgroup
-    // per 16-row tile row) above that and for any n with ORBGPU_BA_CHOL=rows (tests/test_ba_gpu.py).
-    const int NT = (n + 15) / 16;
+// stage 4: Cholesky + solves of the reduced camera system: the register-resident single-workgroup
+// kernel (k_ba_chol_mf2) for n <= 16 x kMfMaxNT = 288, the tile-row kernel (k_ba_chol_rows, one workgroup
+// per 16-row tile row) above that and for any n with ORBGPU_BA_CHOL=rows (tests/test_ba_gpu.py).
+bool ba_select_chol(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    UnitArgs& u = c.u;
+    const int n = u.n, NT = u.NT;
     if (NT > kRowMaxNT) {
-        agree_fail(true);
-        return orbgpu_fail(ORB_ERR_ARG, "more than 682 free keyframes in the local window");
+        ba_agree_fail(c, true);
+        return ba_fail(c, ORB_ERR_ARG, "more than 682 free keyframes in the local window");
     }
     static const char* chol_env = getenv("ORBGPU_BA_CHOL");
     const bool use_rows = n > 0 && (n > 16 * kMfMaxNT || (chol_env && !strcmp(chol_env, "rows")) ||
                                     g_force_rows.load(std::memory_order_relaxed));
     const bool rows_lds = NT <= kRowLdsMaxNT;
-    const size_t rows_lds_bytes =
-        sizeof(double) * ((rows_lds ? (size_t)NT * 256 : 0) + 272 + 256 + 16 + 16 * (size_t)NT);
+    u.use_rows = use_rows ? 1 : 0;
+    u.rows_lds = rows_lds ? 1 : 0;
+    u.rows_lds_bytes = sizeof(double) * ((rows_lds ? (size_t)NT * 256 : 0) + 272 + 256 + 16 + 16 * (size_t)NT);
     if (use_rows) {
         const size_t nflag = 4 + (size_t)NT * NT;
         bool ok2 = h->lpub.grow((size_t)NT * NT * 256) && h->ypub.grow(16 * (size_t)NT) &&
                    (rows_lds || h->racc.grow((size_t)NT * NT * 256));
         if (ok2 && nflag > h->cflag.cap) {  // (re)allocated: epoch and every flag start at 0
-            ok2 = h->cflag.grow(nflag) && hipMemsetAsync(h->cflag.p, 0, nflag * sizeof(unsigned), s) == hipSuccess;
+            ok2 = h->cflag.grow(nflag) && hipMemsetAsync(h->cflag.p, 0, nflag * sizeof(unsigned), c.s) == hipSuccess;
         }
-        if (agree_fail(!ok2)) return orbgpu_fail(ORB_ERR_DEVICE, "BA Cholesky buffers");
+        if (ba_agree_fail(c, !ok2)) return ba_fail(c, ORB_ERR_DEVICE, "BA Cholesky buffers");
     }
+    u.lpub = h->lpub.p;
+    u.ypub = h->ypub.p;
+    u.racc = h->racc.p;
+    u.cflag = h->cflag.p;
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute((const void*)k_ba_chol_mf2<kMf2TileWaves>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMf2Lds);
@@ -2916,439 +2932,194 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
         (void)hipGetLastError();
         attr_set = true;
     }
-    // ORBGPU_BA_TRACE: the first Cholesky of the process records its phase stamps (dump_chol_trace)
-    static int trace_left = getenv("ORBGPU_BA_TRACE") ? 1 : 0;
-    auto launch_chol = [&](const LmState* g, const PoseTail& pt, const double* hpp_add = nullptr,
-                           const double* lam_add = nullptr) {
-        if (use_rows) {
-            if (rows_lds)
-                hipLaunchKernelGGL(k_ba_chol_rows<true>, dim3(NT), dim3(kRowThreads), rows_lds_bytes, s, n, SS,
-                                   BSV, h->x.p, h->status.p, h->lpub.p, h->ypub.p, h->cflag.p, h->racc.p, g,
-                                   (int)kGateTrial);
-            else
-                hipLaunchKernelGGL(k_ba_chol_rows<false>, dim3(NT), dim3(kRowThreads), rows_lds_bytes, s, n, SS,
-                                   BSV, h->x.p, h->status.p, h->lpub.p, h->ypub.p, h->cflag.p, h->racc.p, g,
-                                   (int)kGateTrial);
-            if (pt.pose) hipLaunchKernelGGL(k_u_pose_update, dim3(1), dim3(256), 0, s, pt, (const double*)h->x.p, g);
-            return;
-        }
-        int64_t* tr = nullptr;
-        if (trace_left && h->trace.grow(kTraceLen)) {
-            hipMemsetAsync(h->trace.p, 0, kTraceLen * sizeof(int64_t), s);
-            tr = h->trace.p;
-        }
-        hipLaunchKernelGGL((k_ba_chol_mf2<kMf2TileWaves>), dim3(1), dim3((kMf2TileWaves + 1) * 64), kMf2Lds, s, n,
-                           SS, BSV, h->x.p, h->status.p, tr, g, (int)kGateTrial, hpp_add, lam_add);
-        if (tr) {
-            trace_left = 0;
-            dump_chol_trace(tr, n, s);
-        }
-    };
-    double* bl = BV + n;
-    const size_t hpl_alt = 18 * ne1;  // the second half of the double-buffered Hpl
-    // The device-driven LM loop: no host round trip per trial.  Sharded, its all-reduces are
-    // stream-ordered RCCL calls between the unit's launches (every rank reduces to the same values and
-    // takes the same LM decisions).  The host-driven loop serves ORBGPU_BA_HOST_LM=1 (tested in
-    // tests/test_ba_gpu.py against the oracle).
-    static const bool host_lm_env = getenv("ORBGPU_BA_HOST_LM") != nullptr;
-    const bool dev_lm = !host_lm_env;
-    const LmState* G = dev_lm ? h->lm.p : nullptr;            // gate source for every per-trial kernel
-    const double* lam = dev_lm ? &h->lm.p->lambda : h->h_scal + 5;  // the trial's lambda (device / pinned)
-    // ---- computeActiveErrors + activeRobustChi2 + buildSystem
-    auto launch_build = [&](bool first) -> bool {
-        if (ne)
-            hipLaunchKernelGGL(k_ba_edges<true>, dim3(grid(ne)), dim3(kT), 0, s, ne, h->edges.p, h->cams.p, h->pose.p,
-                               h->point.p, h->pose_h.p, hub, h->err.p, h->rho0.p, h->ecl.p, h->hpl.p, h->ecp.p, G,
-                               (int)kGateBuild);
-        if (nl)
-            hipLaunchKernelGGL(k_ba_reduce_land, dim3(grid(nl)), dim3(kT), 0, s, nl, h->land_off.p, h->land_edge.p,
-                               h->ecl.p, h->hll.p, bl, G, (int)kGateBuild);
-        if (nf) {
-            hipLaunchKernelGGL(k_ba_reduce_pose, dim3(nf), dim3(64), 0, s, h->pose_off.p, h->pose_fl.p, h->ecp.p,
-                               HPP, BV, G, (int)kGateBuild);
-            if (!dev_reduce(h, HPP, 36 * (size_t)nf, ORB_BA_SUM) || !dev_reduce(h, BV, n, ORB_BA_SUM))
-                return false;
-        }
-        if (first)  // (on the device path the gate limits it to iteration 0)
-            hipLaunchKernelGGL(k_ba_maxdiag, dim3(1), dim3(kT), 0, s, nf, nl, HPP, h->hll.p, h->scal.p + 3, G,
-                               (int)kGateBuild0);
-        hipLaunchKernelGGL(k_ba_sums, dim3(1), dim3(1024), 0, s, ne, h->rho0.p, primary ? 0 : n, n + m, lam,
-                           (const double*)nullptr, BV, h->status.p, h->scal.p, dev_lm || dist ? nullptr : h->h_scal,
-                           G, (int)kGateBuild);
-        return true;
-    };
-    // ---- setLambda + BlockSolver::solve + SparseOptimizer::update + computeActiveErrors + computeScale
-    auto launch_trial = [&]() -> bool {
-        if (nfe)
-            hipLaunchKernelGGL(k_ba_schur_edges, dim3(grid(nfe)), dim3(kT), 0, s, nfe, lam, h->landf_edge.p, h->fland.p,
-                               h->hll.p, bl, h->hpl.p, hpl_alt, h->z.p, h->cb.p, G, (int)kGateTrial);
-        if (nf) {
-            hipLaunchKernelGGL(k_ba_schur_blocks, dim3(nblk), dim3(64), 0, s, n, nf, lam, primary ? 1 : 0, h->blk_off.p,
-                               h->pairs.p, h->blk_cnt.p, h->z.p, h->hpl.p, HPP, SS, G, (int)kGateTrial);
-            hipLaunchKernelGGL(k_ba_schur_rhs, dim3(nf), dim3(64), 0, s, h->pose_off.p, h->pose_fl.p, h->cb.p, BV,
-                               primary ? 1 : 0, BSV, G, (int)kGateTrial);
-            if (!dev_reduce(h, SS, (size_t)n * n, ORB_BA_SUM) || !dev_reduce(h, BSV, n, ORB_BA_SUM))
-                return false;
-            launch_chol(G, PoseTail{});
-        } else if (!dev_lm) {
-            hipMemsetAsync(h->status.p, 0, sizeof(int32_t), s);
-        }
-        if (nl)
-            hipLaunchKernelGGL(k_ba_backsub, dim3(grid(nl)), dim3(kT), 0, s, nl, n, lam, h->landf_off.p, h->landf_edge.p,
-                               h->landf_row.p, h->hpl.p, bl, h->hll.p, h->x.p, G, (int)kGateTrial);
-        hipLaunchKernelGGL(k_ba_update, dim3(grid(nf + nl)), dim3(kT), 0, s, nf, nl, n, h->free_pose.p, h->land_point.p,
-                           h->x.p, h->pose.p, h->pose_bak.p, h->point.p, h->point_bak.p, G, (int)kGateTrial);
-        if (ne)
-            hipLaunchKernelGGL(k_ba_edges<false>, dim3(grid(ne)), dim3(kT), 0, s, ne, h->edges.p, h->cams.p, h->pose.p,
-                               h->point.p, h->pose_h.p, hub, h->err.p, h->rho0.p, h->ecl.p, h->hpl.p, h->ecp.p, G,
-                               (int)kGateTrial);
-        hipLaunchKernelGGL(k_ba_sums, dim3(1), dim3(1024), 0, s, ne, h->rho0.p, primary ? 0 : n, n + m, lam,
-                           (const double*)h->x.p, BV, h->status.p, h->scal.p,
-                           dev_lm || dist ? nullptr : h->h_scal, G, (int)kGateTrial);
-        return true;
-    };
-    hipStream_t rs = s;  // the stream of the restore and the results (see the device-driven loop)
-    auto launch_restore = [&]() {
-        hipLaunchKernelGGL(k_ba_restore, dim3(grid(nf + nl)), dim3(kT), 0, rs, nf, nl, h->free_pose.p, h->land_point.p,
-                           h->pose.p, h->pose_bak.p, h->point.p, h->point_bak.p, G, (int)kGateRestore);
-    };
-    // the host loop reads [0] chi2, [1] computeScale, [2] status, [3] max diag (reduced over the ranks)
-    auto read_scalars = [&]() -> bool {
-        if (dist) {
-            if (!dev_reduce(h, h->scal.p, 2, ORB_BA_SUM) || !dev_reduce(h, h->scal.p + 3, 1, ORB_BA_MAX)) return false;
-            hipMemcpyAsync(h->h_scal, h->scal.p, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
-        }
-        return hipStreamSynchronize(s) == hipSuccess;
-    };
+    if (*chol_trace_left() && h->trace.grow(kTraceLen)) u.trace = h->trace.p;
+    return true;
+}
 
-    if (dev_lm) {
-        // One unit per trial: the build's reductions and controller (gated to the start of an
-        // iteration; the linearisation itself comes from the accepted trial, or from the one build
-        // launch before the first unit), the trial, the trial controller, restore on reject.  The host
-        // keeps one unit queued behind the running one and reads the pinned progress after each
-        // unit's event; once the solve is done the queued unit is a run of no-op launches.
-        // (the state's start, the counters and the status went up with the inputs)
-        memset(h->h_prog, 0, sizeof(LmProgress));
-        *h->h_stop = 0;
-        if (dist) {  // the partial buffers; the scalar slots must start at zero (the ranks' max diag slots)
-            const size_t nd = 2 * (36 * (size_t)nf + n + 4 + h->world) + (size_t)n * n + n + 2 * 4;
-            const bool okp = h->dpart.grow(nd) && hipMemsetAsync(h->dpart.p, 0, nd * sizeof(double), s) == hipSuccess;
-            if (agree_fail(!okp)) return orbgpu_fail(ORB_ERR_DEVICE, "BA sharded buffers");
-        }
-        const int nparts = (int)grid(ne), nparts2 = (int)grid(nl + nf);  // partials: edge blocks, vertex blocks
-        double* const pmax = h->part.p + nparts + nparts2;  // k_u_reduce_build's per-block max |diag|
-        LmState* L = h->lm.p;
-        // one unit = 6 launches: reductions (+ chi2, max diag, build controller), Schur edges, Schur
-        // blocks + rhs, Cholesky + solves, back-substitution + update, errors and linearisation at the
-        // new estimate (+ chi2, computeScale, trial controller)
-        // ORBGPU_BA_TRIAL_LIN=1: every trial also linearises at its new estimate, so an accepted
-        // trial leaves nothing for the next build (default off: on MI355X the trial then costs what
-        // the build launch saves, C5 1.590 vs 1.582 ms per solve)
-        static const char* tl_env = getenv("ORBGPU_BA_TRIAL_LIN");
-        const bool trial_lin = tl_env && !strcmp(tl_env, "1");
-        // The trial's back-substitution, update and error pass in one launch instead of two (round 6):
-        // k_u_land_trial moves the poses (each block in LDS, the last one in memory) and the landmarks,
-        // then evaluates the landmarks' edges.  Beyond kT free poses (tile-row Cholesky sizes)
-        // k_u_pose_update moves the poses first.  ORBGPU_BA_FUSED_TRIAL=0: k_u_backsub_update +
-        // k_u_edges_trial.
-        static const char* ft_env = getenv("ORBGPU_BA_FUSED_TRIAL");
-        const bool fused = !trial_lin && !(ft_env && !strcmp(ft_env, "0"));
-        const int pose_mode = nf == 0 ? 0 : nf <= kT ? 1 : 2;
-        const PoseTail pt_unit = PoseTail{h->free_pose.p, h->pose.p, h->pose_bak.p, BV, lam, h->scal.p + 8, nf,
-                                          primary ? 1 : 0};
-        auto launch_edges_build = [&]() {
-            hipLaunchKernelGGL(k_u_edges_build, dim3(nparts), dim3(kT), 0, s, ne, h->edges.p, h->cams.p, h->pose.p,
-                               h->point.p, h->pose_h.p, hub, h->err.p, h->rho0.p, h->ecl.p, h->hpl.p, h->ecp.p,
-                               h->part.p, (const LmState*)L);
-        };
-        if (trial_lin) launch_edges_build();
-        // sharded: the partials [Hpp | b_p | build scalars] (chi2, slots of the ranks' max diag at
-        // 4 + r: one payload, one collective), their sums, [S | b_S], the trial scalars (chi2,
-        // computeScale, stop) and their sums
-        const int nsb = 4 + h->world;
-        const size_t nhb = 36 * (size_t)nf + n;
-        double* const p_hb = dist ? h->dpart.p : nullptr;
-        double* const p_scb = dist ? p_hb + nhb : nullptr;
-        double* const r_hb = dist ? p_scb + nsb : nullptr;
-        double* const r_scb = dist ? r_hb + nhb : nullptr;
-        double* const p_sb = dist ? r_scb + nsb : nullptr;
-        double* const p_sct = dist ? p_sb + (size_t)n * n + n : nullptr;
-        double* const r_sct = dist ? p_sct + 4 : nullptr;
-        bool coll_ok = true;
-        // The fast unit (one process, the single-workgroup Cholesky, the fused trial): 4 launches per trial
-        // instead of 6 -- k_u_land_build (linearisation, Hll / b_l, Z and cb), k_u_schur2 (S without its
-        // diagonal Hpp + lambda I, b_S, Hpp / b_p), the Cholesky (adding Hpp + lambda I as it loads S),
-        // k_u_land_trial.  The solve's first build (lambda from max diag) runs once before the units,
-        // with the build controller.  ORBGPU_BA_FAST_UNIT=0: the 6-launch unit.
-        static const char* fu_env = getenv("ORBGPU_BA_FAST_UNIT");
-        const bool fast = fused && !dist && !use_rows && !(fu_env && !strcmp(fu_env, "0"));
-        auto launch_reduce_build = [&]() {
-            hipLaunchKernelGGL(k_u_reduce_build, dim3(nf + grid(nl, 64)), dim3(64), 0, s, nf, nl, h->pose_off.p,
-                               h->pose_fl.p, h->ecp.p, HPP, BV, h->land_off.p, h->land_edge.p, h->ecl.p, h->hll.p, bl,
-                               h->part.p, nparts, h->counters.p, h->scal.p, L, 0, (double*)nullptr, h->rank, pmax);
-        };
-        if (fast) {  // the solve's first build (gated to phase 0, i.e. before any unit has run)
-            launch_edges_build();
-            launch_reduce_build();
-        }
-        auto unit_launches = [&]() {
-            if (fast) {
-                hipLaunchKernelGGL(k_u_land_build, dim3(grid((size_t)nl * kLB)), dim3(kT), 0, s, nl, lam, h->land_off.p,
-                                   h->land_edge.p, h->edges.p, h->cams.p, h->pose.p, h->point.p, h->pose_h.p, hub,
-                                   h->err.p, h->rho0.p, h->hpl.p, h->ecp.p, h->hll.p, bl, h->z.p, h->cb.p,
-                                   (const LmState*)L);
-                if (nf) {
-                    hipLaunchKernelGGL(k_u_schur2, dim3(nblk + 2 * nf), dim3(64), 0, s, n, nf, nblk, lam, h->blk_off.p,
-                                       h->pairs.p, h->blk_cnt.p, h->pose_off.p, h->pose_fl.p, h->z.p, h->hpl.p, h->ecp.p,
-                                       HPP, BV, SS, h->cb.p, BSV, (const LmState*)L);
-                    launch_chol((const LmState*)L, PoseTail{}, HPP, lam);
-                }
-                hipLaunchKernelGGL(k_u_land_trial, dim3(grid(nl)), dim3(kLT), 0, s, nl, n, lam, h->landf_off.p,
-                                   h->landf_edge.p, h->landf_row.p, h->hpl.p, hpl_alt, bl, h->hll.p, h->x.p,
-                                   h->land_point.p, h->point.p, h->point_bak.p, h->land_off.p, h->land_edge.p,
-                                   h->edges.p, h->cams.p, h->pose.p, h->pose_h.p, pt_unit, pose_mode, hub, h->err.p,
-                                   h->rho0.p, h->part.p, h->part.p + nparts, h->counters.p + 1, h->status.p, h->scal.p,
-                                   L, h->h_prog, 0, (double*)nullptr, (const volatile int32_t*)h->h_stop, 1);
-                return;
-            }
-            if (!trial_lin) launch_edges_build();
-            hipLaunchKernelGGL(k_u_reduce_build, dim3(nf + grid(nl, 64)), dim3(64), 0, s, nf, nl, h->pose_off.p,
-                               h->pose_fl.p, h->ecp.p, dist ? p_hb : HPP, dist ? p_hb + 36 * (size_t)nf : BV,
-                               h->land_off.p, h->land_edge.p, h->ecl.p, h->hll.p, bl, h->part.p, nparts, h->counters.p,
-                               h->scal.p, L, dist ? 1 : 0, p_scb, h->rank, pmax);
-            if (dist) {  // one collective for [Hpp | b_p | build scalars], then the sums into place
-                coll_ok = coll_ok && dev_reduce2(h, p_hb, r_hb, nhb + nsb, ORB_BA_SUM) &&
-                          hipMemcpyAsync(HPP, r_hb, nhb * sizeof(double), hipMemcpyDeviceToDevice, s) == hipSuccess;
-                hipLaunchKernelGGL(k_lm_build_ctl, dim3(1), dim3(64), 0, s, nf, (const double*)HPP, (const double*)r_scb,
-                                   h->world, h->scal.p, L);
-            }
-            if (nfe)
-                hipLaunchKernelGGL(k_ba_schur_edges, dim3(grid(nfe)), dim3(kT), 0, s, nfe, lam, h->landf_edge.p,
-                                   h->fland.p, h->hll.p, bl, h->hpl.p, hpl_alt, h->z.p, h->cb.p, (const LmState*)L,
-                                   (int)kGateTrial);
-            if (nf) {
-                hipLaunchKernelGGL(k_u_schur, dim3(nblk + nf), dim3(64), 0, s, n, nf, nblk, lam, h->blk_off.p,
-                                   h->pairs.p, h->blk_cnt.p, h->pose_off.p, h->pose_fl.p, h->z.p, h->hpl.p, hpl_alt, HPP,
-                                   dist ? p_sb : SS, h->cb.p, BV, dist ? p_sb + (size_t)n * n : BSV, (const LmState*)L,
-                                   primary ? 1 : 0);
-                if (dist) coll_ok = coll_ok && dev_reduce2(h, p_sb, SS, (size_t)n * n + n, ORB_BA_SUM);
-                launch_chol((const LmState*)L, fused && pose_mode == 2 ? pt_unit : PoseTail{});
-            }
-            if (fused) {
-                hipLaunchKernelGGL(k_u_land_trial, dim3(grid(nl)), dim3(kLT), 0, s, nl, n, lam, h->landf_off.p,
-                                   h->landf_edge.p, h->landf_row.p, h->hpl.p, hpl_alt, bl, h->hll.p, h->x.p,
-                                   h->land_point.p, h->point.p, h->point_bak.p, h->land_off.p, h->land_edge.p,
-                                   h->edges.p, h->cams.p, h->pose.p, h->pose_h.p, pt_unit, pose_mode, hub, h->err.p,
-                                   h->rho0.p, h->part.p, h->part.p + nparts, h->counters.p + 1, h->status.p, h->scal.p,
-                                   L, h->h_prog, dist ? 1 : 0, p_sct,
-                                   (const volatile int32_t*)h->h_stop, 0);
-            } else {
-            hipLaunchKernelGGL(k_u_backsub_update, dim3(nparts2), dim3(kT), 0, s, nl, nf, n, lam, h->landf_off.p,
-                               h->landf_edge.p, h->landf_row.p, h->hpl.p, hpl_alt, bl, h->hll.p, h->x.p, BV,
-                               h->free_pose.p, h->land_point.p, h->pose.p, h->pose_bak.p, h->point.p, h->point_bak.p,
-                               h->part.p + nparts, (const LmState*)L, primary ? 1 : 0);
-            hipLaunchKernelGGL(trial_lin ? k_u_edges_trial<true> : k_u_edges_trial<false>, dim3(nparts), dim3(kT), 0, s,
-                               ne, h->edges.p, h->cams.p, h->pose.p, h->point.p, h->pose_h.p, hub, h->err.p, h->rho0.p,
-                               h->ecl.p, h->hpl.p, hpl_alt, h->ecp.p, h->part.p, h->counters.p + 1, h->part.p + nparts,
-                               nparts2, h->status.p, h->scal.p, L, h->h_prog, dist ? 1 : 0, p_sct,
-                               (const volatile int32_t*)h->h_stop);
-            }
-            if (dist) {
-                coll_ok = coll_ok && dev_reduce2(h, p_sct, r_sct, 4, ORB_BA_SUM);
-                hipLaunchKernelGGL(trial_lin ? k_lm_trial_ctl<true> : k_lm_trial_ctl<false>, dim3(1), dim3(64), 0, s,
-                                   (const double*)r_sct, (const int32_t*)h->status.p, h->scal.p, L, h->h_prog);
-            }
-        };
-        // Every unit launches the same kernels with the same arguments (the device state gates them),
-        // so the unit is captured once as a graph and replayed: one graph launch instead of 7 kernel
-        // launches per trial.  The capture is kept while the arguments (sizes, buffers) are unchanged.
-        auto dbits = [](double v) { uintptr_t u; memcpy(&u, &v, sizeof(u)); return u; };
-        bool use_graph = !trace_left && !dist;  // (the trace dump synchronises the stream: not capturable;
-                                                // sharded, the collectives stay direct calls)
-        // four units per graph launch: each launch boundary costs ~13 us on the device, a gated no-op
-        // unit behind the last trial about as much (round 6, the 4-launch fast unit, C5 mono solve:
-        // 2 units 1.410 / 1.436 ms, 3: 1.397 / 1.377, 4: 1.368 / 1.381, 8: 1.356 / 1.360; 4 keeps the
-        // waste of a 9-12-trial solve small, profiles/r06/ba_units_ab_r06.txt)
-        // With a stop flag, one unit per launch: the host polls the flag after every launch, so at
-        // most two trials (the running and the queued unit) follow a raised flag, as before.
-        static const char* upl_env = getenv("ORBGPU_BA_UNITS");  // (A/B of the units per graph launch)
-        const int upl_default = upl_env ? std::max(1, std::min(16, atoi(upl_env))) : 4;
-        const int units_per_launch = (opt->stop_flag || opt->stop_flag_bool) ? 1 : upl_default;
-        if (use_graph) {
-            const std::vector<uintptr_t> key = {
-                (uintptr_t)s, (uintptr_t)n, (uintptr_t)m, (uintptr_t)ne, (uintptr_t)nf, (uintptr_t)nl, (uintptr_t)nfe,
-                (uintptr_t)nblk, (uintptr_t)nparts, (uintptr_t)units_per_launch, dbits(hub.delta_mono), dbits(hub.delta_stereo), (uintptr_t)bl,
-                (uintptr_t)h->edges.p, (uintptr_t)h->cams.p, (uintptr_t)h->pose.p, (uintptr_t)h->point.p,
-                (uintptr_t)h->pose_h.p, (uintptr_t)h->err.p, (uintptr_t)h->rho0.p, (uintptr_t)h->ecl.p,
-                (uintptr_t)h->hpl.p, (uintptr_t)h->ecp.p, (uintptr_t)h->part.p, (uintptr_t)h->pose_off.p,
-                (uintptr_t)h->pose_fl.p, (uintptr_t)HPP, (uintptr_t)BV, (uintptr_t)h->land_off.p,
-                (uintptr_t)h->land_edge.p, (uintptr_t)h->hll.p, (uintptr_t)h->counters.p, (uintptr_t)h->scal.p,
-                (uintptr_t)L, (uintptr_t)lam, (uintptr_t)h->landf_edge.p, (uintptr_t)h->fland.p, (uintptr_t)h->z.p,
-                (uintptr_t)h->cb.p, (uintptr_t)SS, (uintptr_t)h->blk_off.p, (uintptr_t)h->pairs.p,
-                (uintptr_t)h->blk_cnt.p, (uintptr_t)BSV,
-                (uintptr_t)h->x.p, (uintptr_t)h->status.p, (uintptr_t)h->landf_off.p, (uintptr_t)h->landf_row.p, (uintptr_t)h->free_pose.p,
-                (uintptr_t)h->land_point.p, (uintptr_t)h->pose_bak.p, (uintptr_t)h->point_bak.p, (uintptr_t)h->h_prog,
-                (uintptr_t)use_rows, (uintptr_t)trial_lin, (uintptr_t)fused, (uintptr_t)fast, (uintptr_t)h->lpub.p, (uintptr_t)h->ypub.p, (uintptr_t)h->cflag.p,
-                (uintptr_t)h->racc.p};
-            if (!h->unit_exec || key != h->unit_key) {
-                if (h->unit_exec) { hipGraphExecDestroy(h->unit_exec); h->unit_exec = nullptr; }
-                if (h->unit_graph) { hipGraphDestroy(h->unit_graph); h->unit_graph = nullptr; }
-                bool ok = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    for (int r = 0; r < units_per_launch; ++r) unit_launches();
-                    ok = hipStreamEndCapture(s, &h->unit_graph) == hipSuccess && h->unit_graph &&
-                         hipGraphInstantiate(&h->unit_exec, h->unit_graph, nullptr, nullptr, 0) == hipSuccess;
-                }
-                if (!ok) {  // fall back to direct launches
-                    (void)hipGetLastError();
-                    if (h->unit_graph) { hipGraphDestroy(h->unit_graph); h->unit_graph = nullptr; }
-                    h->unit_exec = nullptr;
-                    use_graph = false;
-                } else {
-                    h->unit_key = key;
-                }
-            }
-        }
-        auto unit = [&](int u) -> bool {
-            if (dist) *h->h_stop = stop_requested(opt) ? 1 : 0;  // read by the trial's last block
-            if (use_graph) {
-                if (hipGraphLaunch(h->unit_exec, s) != hipSuccess) return false;
-            } else {
-                for (int r = 0; r < units_per_launch; ++r) unit_launches();
-            }
-            // sharded: the ranks must launch the same number of units (each one issues collectives).
-            // The pinned progress is written by the unit's last kernel, which may or may not have run
-            // when the host looks at it one unit later; `done` as this unit left it is the same on
-            // every rank.
-            if (dist && hipMemcpyAsync(&h->h_stop[1 + (u & 1)], &L->done, sizeof(int32_t), hipMemcpyDeviceToHost, s) !=
-                            hipSuccess)
-                return false;
-            return hipEventRecord(h->unit_ev[u & 1], s) == hipSuccess;
-        };
-        auto done_after = [&](int u) -> bool { return dist ? h->h_stop[1 + (u & 1)] != 0 : h->h_prog->done != 0; };
-        const int max_units = (std::max(0, opt->iterations) * 10 + units_per_launch - 1) / units_per_launch;
-        if (max_units > 0) {
-            if (!unit(0)) return orbgpu_fail(ORB_ERR_DEVICE, "BA launch failed");
-            for (int u = 1;; ++u) {
-                const bool more = u < max_units;
-                if (more && !unit(u)) return orbgpu_fail(ORB_ERR_DEVICE, "BA launch failed");
-                if (hipEventSynchronize(h->unit_ev[(u - 1) & 1]) != hipSuccess)
-                    return orbgpu_fail(ORB_ERR_DEVICE, "BA device error");
-                if (trace && n_unit_t < 32) unit_t[n_unit_t++] = us(t_pack, clk::now());
-                if (done_after(u - 1) && more) {
-                    // the solve ended inside unit u-1 and unit u, queued behind it, is a run of gated
-                    // no-op launches: the restore and the results go on the tail stream beside it
-                    if (hipStreamWaitEvent(h->tail, h->unit_ev[(u - 1) & 1], 0) != hipSuccess)
-                        return orbgpu_fail(ORB_ERR_DEVICE, "BA device error");
-                    rs = h->tail;
-                }
-                if (!coll_ok) return orbgpu_fail(ORB_ERR_DEVICE, "BA collective failed");
-                if (done_after(u - 1) || !more) break;
-                // (the queued unit is live: the tail stays on s; sharded, the ranks agree on the stop on
-                // the device instead, so that every rank launches the same collectives)
-                if (!dist && stop_requested(opt)) break;
-            }
-        }
-        launch_restore();  // undo a rejected last trial (gated on the device state)
-        // (the progress record is read after the results' synchronisation below)
-    } else {
-        double lambda = 0, ni = 2;
-        int nBad = 0, it = 0;
-        for (; it < opt->iterations && !stop(); ++it) {
-            if (!launch_build(it == 0) || !read_scalars()) return orbgpu_fail(ORB_ERR_DEVICE, "BA build failed");
-            double currentChi = h->h_scal[0];
-            const double iniChi = currentChi;
-            if (it == 0) {
-                res->initial_chi2 = currentChi;
-                lambda = opt->user_lambda_init > 0 ? opt->user_lambda_init : tau * h->h_scal[3];
-                ni = 2;
-                nBad = 0;
-            }
-            double rho = 0;
-            int qmax = 0;
-            do {
-                h->h_scal[5] = lambda;  // read by the trial kernels (the stream is idle here)
-                if (!launch_trial() || !read_scalars()) return orbgpu_fail(ORB_ERR_DEVICE, "BA trial failed");
-                res->trials++;
-                double tempChi = h->h_scal[0];
-                if (h->h_scal[2] != 0.0) tempChi = std::numeric_limits<double>::max();  // not positive definite
-                rho = currentChi - tempChi;
-                double scale = h->h_scal[1] + 1e-3;
-                rho /= scale;
-                if (rho > 0 && std::isfinite(tempChi)) {
-                    double alpha = 1. - std::pow((2 * rho - 1), 3);
-                    alpha = std::min(alpha, 2. / 3.);
-                    lambda *= std::max(1. / 3., alpha);
-                    ni = 2;
-                    currentChi = tempChi;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    launch_restore();
-                }
-                qmax++;
-            } while (rho < 0 && qmax < 10 && !stop());
-            res->final_chi2 = currentChi;
-            if (qmax == 10 || rho == 0) { res->terminated = 1; ++it; break; }
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-            else nBad = 0;
-            if (nBad >= 3) { res->terminated = 1; ++it; break; }
-        }
-        res->iterations = it;
-        res->lambda = lambda;
+// stage 5: which unit runs, the sharded unit's partial buffers, and the fast unit's first build.  (The
+// LM state's start, the counters and the status went up with the inputs.)
+bool ba_prepare_units(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    UnitArgs& u = c.u;
+    const int n = u.n, nf = u.nf;
+    memset(h->h_prog, 0, sizeof(LmProgress));
+    *h->h_stop = 0;
+    if (c.dist) {
+        // the partials [Hpp | b_p | build scalars] (chi2, slots of the ranks' max diag at 4 + r: one
+        // payload, one collective), their sums, [S | b_S], the trial scalars (chi2, computeScale, stop)
+        // and their sums; the scalar slots must start at zero (the ranks' max diag slots)
+        const size_t nsb = 4 + h->world, nhb = 36 * (size_t)nf + n;
+        const size_t nd = 2 * (nhb + nsb) + (size_t)n * n + n + 2 * 4;
+        const bool okp = h->dpart.grow(nd) && hipMemsetAsync(h->dpart.p, 0, nd * sizeof(double), c.s) == hipSuccess;
+        if (ba_agree_fail(c, !okp)) return ba_fail(c, ORB_ERR_DEVICE, "BA sharded buffers");
+        u.coll = h;
+        u.p_hb = h->dpart.p;
+        u.p_scb = u.p_hb + nhb;
+        u.r_hb = u.p_scb + nsb;
+        u.r_scb = u.r_hb + nhb;
+        u.p_sb = u.r_scb + nsb;
+        u.p_sct = u.p_sb + (size_t)n * n + n;
+        u.r_sct = u.p_sct + 4;
     }
-    res->stopped = stop() ? 1 : 0;
-    t_solve = clk::now();
-    // results through the pinned buffer sized before the solve, written by one kernel (edge chi2 / depth
-    // flags, the poses and points): no device-to-host copies
+    // ORBGPU_BA_FAST_UNIT=0: the 6-launch unit on one process too
+    static const char* fu_env = getenv("ORBGPU_BA_FAST_UNIT");
+    u.fast = !c.dist && !u.use_rows && !(fu_env && !strcmp(fu_env, "0"));
+    if (u.fast) {  // the solve's first build (gated to phase 0, i.e. before any unit has run)
+        launch_edges_build(u);
+        launch_reduce_build(u);
+    }
+    return true;
+}
+
+// stage 6: every unit launches the same kernels with the same arguments, so the units of one graph
+// launch are captured once and replayed: one graph launch instead of 4 or 6 kernel launches per trial.
+// The capture is kept while the arguments (UnitArgs, byte for byte) are unchanged.
+void ba_capture_units(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    UnitArgs& u = c.u;
+    c.use_graph = !*chol_trace_left() && !c.dist;  // (the trace dump synchronises the stream: not capturable;
+                                                  // sharded, the collectives stay direct calls)
+    // four units per graph launch: each launch boundary costs ~13 us on the device, a gated no-op
+    // unit behind the last trial about as much (round 6, the 4-launch fast unit, C5 mono solve:
+    // 2 units 1.410 / 1.436 ms, 3: 1.397 / 1.377, 4: 1.368 / 1.381, 8: 1.356 / 1.360; 4 keeps the
+    // waste of a 9-12-trial solve small, profiles/r06/ba_units_ab_r06.txt)
+    // With a stop flag, one unit per launch: the host polls the flag after every launch, so at
+    // most two trials (the running and the queued unit) follow a raised flag, as before.
+    static const char* upl_env = getenv("ORBGPU_BA_UNITS");  // (A/B of the units per graph launch)
+    const int upl_default = upl_env ? std::max(1, std::min(16, atoi(upl_env))) : 4;
+    u.units_per_launch = (c.opt->stop_flag || c.opt->stop_flag_bool) ? 1 : upl_default;
+    if (!c.use_graph) return;
+    if (h->unit_exec && !memcmp(&h->unit_key, &u, sizeof(UnitArgs))) return;
+    if (h->unit_exec) { hipGraphExecDestroy(h->unit_exec); h->unit_exec = nullptr; }
+    if (h->unit_graph) { hipGraphDestroy(h->unit_graph); h->unit_graph = nullptr; }
+    bool coll_ok = true;  // (no collectives on this path)
+    bool ok = hipStreamBeginCapture(c.s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        for (int r = 0; r < u.units_per_launch; ++r) launch_unit(u, coll_ok);
+        ok = hipStreamEndCapture(c.s, &h->unit_graph) == hipSuccess && h->unit_graph &&
+             hipGraphInstantiate(&h->unit_exec, h->unit_graph, nullptr, nullptr, 0) == hipSuccess;
+    }
+    if (!ok) {  // fall back to direct launches
+        (void)hipGetLastError();
+        if (h->unit_graph) { hipGraphDestroy(h->unit_graph); h->unit_graph = nullptr; }
+        h->unit_exec = nullptr;
+        c.use_graph = false;
+    } else {
+        memcpy(&h->unit_key, &u, sizeof(UnitArgs));
+    }
+}
+
+// stage 7: the host keeps one graph launch (or its direct launches) queued behind the running one and
+// reads the pinned progress after each one's event; once the solve is done the queued one is a run of
+// no-op launches, and the restore and the results go on the tail stream beside it.
+bool ba_drive(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    const UnitArgs& u = c.u;
+    const bool dist = c.dist;
+    const hipStream_t s = c.s;
+    bool coll_ok = true;
+    auto unit = [&](int k) -> bool {
+        if (dist) *h->h_stop = stop_requested(c.opt) ? 1 : 0;  // read by the trial's last block
+        if (c.use_graph) {
+            if (hipGraphLaunch(h->unit_exec, s) != hipSuccess) return false;
+        } else {
+            for (int r = 0; r < u.units_per_launch; ++r) launch_unit(u, coll_ok);
+        }
+        // sharded: the ranks must launch the same number of units (each one issues collectives).
+        // The pinned progress is written by the unit's last kernel, which may or may not have run
+        // when the host looks at it one unit later; `done` as this unit left it is the same on
+        // every rank.
+        if (dist && hipMemcpyAsync(&h->h_stop[1 + (k & 1)], &u.lm->done, sizeof(int32_t), hipMemcpyDeviceToHost, s) !=
+                        hipSuccess)
+            return false;
+        return hipEventRecord(h->unit_ev[k & 1], s) == hipSuccess;
+    };
+    auto done_after = [&](int k) -> bool { return dist ? h->h_stop[1 + (k & 1)] != 0 : h->h_prog->done != 0; };
+    const int max_units = (std::max(0, c.opt->iterations) * 10 + u.units_per_launch - 1) / u.units_per_launch;
+    if (max_units > 0) {
+        if (!unit(0)) return ba_fail(c, ORB_ERR_DEVICE, "BA launch failed");
+        for (int k = 1;; ++k) {
+            const bool more = k < max_units;
+            if (more && !unit(k)) return ba_fail(c, ORB_ERR_DEVICE, "BA launch failed");
+            if (hipEventSynchronize(h->unit_ev[(k - 1) & 1]) != hipSuccess)
+                return ba_fail(c, ORB_ERR_DEVICE, "BA device error");
+            if (ba_trace_on() && c.n_unit_t < 32) c.unit_t[c.n_unit_t++] = us_between(c.t_pack, clk::now());
+            if (done_after(k - 1) && more) {
+                // the solve ended inside launch k-1 and launch k, queued behind it, is a run of gated
+                // no-op launches: the restore and the results go on the tail stream beside it
+                if (hipStreamWaitEvent(h->tail, h->unit_ev[(k - 1) & 1], 0) != hipSuccess)
+                    return ba_fail(c, ORB_ERR_DEVICE, "BA device error");
+                c.rs = h->tail;
+            }
+            if (!coll_ok) return ba_fail(c, ORB_ERR_DEVICE, "BA collective failed");
+            if (done_after(k - 1) || !more) break;
+            // (the queued launch is live: the tail stays on s; sharded, the ranks agree on the stop on
+            // the device instead, so that every rank launches the same collectives)
+            if (!dist && stop_requested(c.opt)) break;
+        }
+    }
+    launch_restore(u, c.rs);
+    return true;
+}
+
+// stage 8: results through the pinned buffer sized before the solve, written by one kernel (edge chi2 /
+// depth flags, the poses and points): no device-to-host copies; the LM outcome from the progress record.
+// Sharded: each rank contributes its landmarks (rank 0 also the points without edges) and its edges'
+// chi2 / depth flags to one SUM all-reduce of the zero-padded arrays.
+int ba_results(BaSolve& c) {
+    orb_ba_s* h = c.h;
+    orb_ba_problem_t* pr = c.pr;
+    orb_ba_result_t* res = c.res;
+    const orbgpu_ba::BaStructure& T = h->st;
+    const int np = c.np, nq = c.nq, ne_all = c.ne_all, ne = c.u.ne;
+    const hipStream_t s = c.s;
+    res->stopped = ba_stop(c) ? 1 : 0;
+    c.t_solve = clk::now();
     double* const dpose = reinterpret_cast<double*>(h->h_dl);
     double* const pts = dpose + 7 * (size_t)np;
     double* const lchi = pts + 3 * (size_t)nq;
-    uint8_t* const ldep = reinterpret_cast<uint8_t*>(lchi + ne1);
+    uint8_t* const ldep = reinterpret_cast<uint8_t*>(lchi + c.ne1);
     {
         const int nt = std::max(std::max(7 * np, 3 * nq), ne);
         if (nt > 0)
-            hipLaunchKernelGGL(k_ba_results, dim3(grid(nt)), dim3(kT), 0, rs, np, nq, ne, h->edges.p, h->pose.p,
+            hipLaunchKernelGGL(k_ba_results, dim3(grid(nt)), dim3(kT), 0, c.rs, np, nq, ne, h->edges.p, h->pose.p,
                                h->point.p, h->err.p, dpose, pts, lchi, ldep);
     }
-    if (hipStreamSynchronize(rs) != hipSuccess) return orbgpu_fail(ORB_ERR_DEVICE, "BA device error");
-    if (dev_lm) {
-        const LmProgress pg = *h->h_prog;
-        res->iterations = pg.it;
-        res->trials = pg.trials;
-        res->terminated = pg.terminated;
-        res->initial_chi2 = pg.initial_chi;
-        res->final_chi2 = pg.final_chi;
-        res->lambda = pg.lambda;
-    }
+    if (hipStreamSynchronize(c.rs) != hipSuccess) return orbgpu_fail(ORB_ERR_DEVICE, "BA device error");
+    const LmProgress pg = *h->h_prog;
+    res->iterations = pg.it;
+    res->trials = pg.trials;
+    res->terminated = pg.terminated;
+    res->initial_chi2 = pg.initial_chi;
+    res->final_chi2 = pg.final_chi;
+    res->lambda = pg.lambda;
     memcpy(pr->pose, dpose, sizeof(double) * 7 * (size_t)np);
-    if (!dist) {
+    if (!c.dist) {
         memcpy(pr->point, pts, sizeof(double) * 3 * (size_t)nq);
         for (int e = 0; e < ne; ++e) {
-            if (edge_chi2) edge_chi2[e] = lchi[e];
-            if (edge_depth_ok) edge_depth_ok[e] = ldep[e];
+            if (c.edge_chi2) c.edge_chi2[e] = lchi[e];
+            if (c.edge_depth_ok) c.edge_depth_ok[e] = ldep[e];
         }
-        if (trace)
+        if (ba_trace_on())
             fprintf(stderr, "[ba] structure %.1f us (order %.1f, csr %.1f, pairs %.1f, rest %.1f), pack %.1f us, upload+LM %.1f us, "
                             "results %.1f us, it %d trials %d\n",
-                    us(t_in, t_struct), us(t_in, t_order), us(t_order, t_csr), us(t_csr, t_pairs), us(t_pairs, t_struct),
-                    us(t_struct, t_pack), us(t_pack, t_solve), us(t_solve, clk::now()), res->iterations, res->trials);
-        if (trace && n_unit_t) {
+                    us_between(c.t_in, c.t_struct), us_between(c.t_in, c.t_order), us_between(c.t_order, c.t_csr),
+                    us_between(c.t_csr, c.t_pairs), us_between(c.t_pairs, c.t_struct), us_between(c.t_struct, c.t_pack),
+                    us_between(c.t_pack, c.t_solve), us_between(c.t_solve, clk::now()), res->iterations, res->trials);
+        if (ba_trace_on() && c.n_unit_t) {
             fprintf(stderr, "[ba] launches seen done at");
-            for (int i = 0; i < n_unit_t; ++i) fprintf(stderr, " %.1f", unit_t[i]);
+            for (int i = 0; i < c.n_unit_t; ++i) fprintf(stderr, " %.1f", c.unit_t[i]);
             fprintf(stderr, " us\n");
         }
         return ORB_OK;
     }
-    // gather: each rank contributes its landmarks (rank 0 also the points without edges) and its
-    // edges' chi2 / depth flags; one SUM all-reduce of the zero-padded arrays
     const size_t nred = 3 * (size_t)nq + 2 * (size_t)ne_all;
     std::vector<double> contrib(nred, 0.0);
     for (int q = 0; q < nq; ++q)
-        if (point_l[q] >= 0 || (primary && qdeg[q] == 0))
+        if (T.point_l[q] >= 0 || (c.primary && T.qdeg[q] == 0))
             for (int k = 0; k < 3; ++k) contrib[3 * (size_t)q + k] = pts[3 * (size_t)q + k];
     for (int e = 0; e < ne; ++e) {
-        const int ge = lmap.empty() ? e : lmap[e];  // (one rank: the structure keeps the edge order)
+        const int ge = T.lmap.empty() ? e : T.lmap[e];  // (one rank: the structure keeps the edge order)
         contrib[3 * (size_t)nq + ge] = lchi[e];
         contrib[3 * (size_t)nq + ne_all + ge] = ldep[e] ? 1.0 : 0.0;
     }
@@ -3360,10 +3131,27 @@ int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* op
         return orbgpu_fail(ORB_ERR_DEVICE, "BA result all-reduce failed");
     memcpy(pr->point, contrib.data(), sizeof(double) * 3 * (size_t)nq);
     for (int e = 0; e < ne_all; ++e) {
-        if (edge_chi2) edge_chi2[e] = contrib[3 * (size_t)nq + e];
-        if (edge_depth_ok) edge_depth_ok[e] = contrib[3 * (size_t)nq + ne_all + e] != 0.0;
+        if (c.edge_chi2) c.edge_chi2[e] = contrib[3 * (size_t)nq + e];
+        if (c.edge_depth_ok) c.edge_depth_ok[e] = contrib[3 * (size_t)nq + ne_all + e] != 0.0;
     }
     return ORB_OK;
+}
+
+}  // namespace
+
+int orb_ba_optimize(orb_ba_t h, orb_ba_problem_t* pr, const orb_ba_options_t* opt, double* edge_chi2,
+                    uint8_t* edge_depth_ok, orb_ba_result_t* res) {
+    if (!h || !pr || !opt || !res) return orbgpu_fail(ORB_ERR_ARG, "null BA argument");
+    memset(res, 0, sizeof(*res));
+    BaSolve c{h, pr, opt, edge_chi2, edge_depth_ok, res};
+    memset(&c.u, 0, sizeof(c.u));
+    c.t_in = c.t_struct = c.t_solve = c.t_order = c.t_csr = c.t_pairs = c.t_pack = clk::now();
+    if (!ba_validate(c) || !ba_upload_raw(c) || !ba_structure(c) || !ba_upload_structure(c) || !ba_select_chol(c) ||
+        !ba_prepare_units(c))
+        return c.rc;
+    ba_capture_units(c);
+    if (!ba_drive(c)) return c.rc;
+    return ba_results(c);
 }
 
 }  // extern "C"
