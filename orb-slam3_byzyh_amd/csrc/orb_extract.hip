@@ -3,8 +3,9 @@
 //
 //   k_pyramid_level  per level: the level view (INTER_LINEAR from the previous level) + a 3-px
 //                    REFLECT_101 border inside the 19-px padded plane, one LDS tile pass
-//   k_fast_cells     one wave per (frame, FAST cell): threshold-independent FAST-9 score, 3x3 NMS
-//                    inside the cell window, iniTh/minTh choice, row-major candidate emission
+//   k_fast_cells     one wave per (frame, FAST cell): compass filter at both thresholds, FAST-9 score
+//                    and 3x3 NMS inside the cell window at iniTh, again at minTh only if nothing
+//                    survives, row-major candidate emission
 //   k_quadtree_kp    one 256-thread workgroup per (frame, level): DistributeOctTree with exact list and
 //                    std::sort semantics (keys stay put, node ids move), plus each keypoint's
 //                    vLappingArea class rank (level-0 scaling, src:1656-1676)
@@ -825,30 +826,62 @@ __device__ __forceinline__ void fast_cell(const KernelGeom& g, const CellDesc& C
         for (int k = 0; k < 16; ++k) off[k] = cx[k] + cy[k] * ws;
     }
     const int ini = g.ini_th, mint = g.min_th;
-    // 1a. compass filter at minTh: a 9-pixel arc always contains two circle pixels 4 apart among
-    //     {0, 4, 8, 12}, so only pixels with such a bright or dark pair can be corners.  Passing
-    //     pixels are compacted (row-major) into cl[].
+    // 1. compass filter at iniTh and minTh in one pass: a 9-pixel arc always contains two circle
+    //    pixels 4 apart among {0, 4, 8, 12}, so only pixels with such a bright or dark pair can be
+    //    corners.  The pixels passing at iniTh are compacted (row-major) into cl[]; the minTh bits are
+    //    parked in registers for the cells that yield nothing at iniTh (2.).
+    // Eight pixels per lane (an octet of one detectable row); items are row-major octets, so the
+    // compaction (one wave scan per 8 pixels) stays row-major.  Lane l takes item 64 k + l in round k
+    // and keeps that octet's minTh bits in byte k of `parked`: one word covers the 4 rounds of a
+    // fixed-stride window (at most 6 octets x 42 rows), four words the 1024 octets build_geometry admits.
+    constexpr int kParkWords = kWS ? 1 : 4;
+    uint32_t parked[kParkWords] = {};
+    const int no = nd > 0 ? (dw + 7) >> 3 : 1, nitems = nd > 0 ? dh * no : 0;
+    // item -> (row, octet): one division here, then a fixed (row, octet) step of 64 items per round
+    const int r0 = lane / no, o0 = lane - r0 * no, dr = 64 / no, dq = 64 - dr * no;
+    auto next_item = [&](int& r, int& o) {
+        o += dq;
+        r += dr;
+        if (o >= no) { o -= no; ++r; }
+    };
     int nlist = 0;
-    if (nd > 0) {
-        // Eight pixels per lane (an octet of one detectable row), as u16 pairs: the centre, left (x-3),
-        // right (x+3) bytes of the row and the up / down (y-/+3) bytes come from three aligned LDS
-        // dwords and two v_alignbyte each, and a bright (dark) adjacent compass pair <=> the largest
-        // pairwise minimum exceeds v + t (the smallest pairwise maximum plus t is below v), with
-        // v_pk_min/max_u16 and saturating v_pk_sub_u16.  Items are row-major octets, so the compaction
-        // (one wave scan per 8 pixels) stays row-major.
-        const int no = (dw + 7) >> 3, nitems = dh * no;
+    auto append = [&](unsigned bits, int row, int oct) {  // the set pixels of one octet per lane -> cl[]
+        const int cnt = __popc(bits);
+        const int incl = wave_incl_scan_dpp(cnt);
+        int pos = nlist + incl - cnt;
+        const int base_idx = ((row + 3) << 7) + 8 * oct + 3;  // (row << 7 | column), window coordinates
+        while (bits) {
+            const int k = __builtin_ctz(bits);
+            bits &= bits - 1u;
+            cl[pos++] = (uint16_t)(base_idx + k);
+        }
+        nlist += __builtin_amdgcn_readlane(incl, 63);
+    };
+    {
+        // The pixels as u16 pairs: the centre, left (x-3), right (x+3) bytes of the row and the up /
+        // down (y-/+3) bytes come from three aligned LDS dwords each, and one v_perm_b32 per pixel pair
+        // both aligns (bytes s .. s+3 of a dword pair, s = the operand's byte offset & 3) and
+        // zero-extends.  s is per cell, so the selectors are wave-uniform and live in SGPRs.
+        // A bright (dark) adjacent compass pair <=> the largest pairwise minimum exceeds v + t (the
+        // smallest pairwise maximum plus t is below v), with v_pk_min/max_u16 and saturating v_pk_sub_u16.
         const uint32_t* wrow = reinterpret_cast<const uint32_t*>(win - shift);  // aligned window rows
         const int wsw = ws >> 2;
-        const u16x2 tt = w16(mint, mint);
-        // bytes [8o + off .. +7] of an aligned row (off includes the row's shift) as two dwords
-        auto ext8 = [&](const uint32_t* row, int o, int off, uint32_t& a, uint32_t& b) {
+        const u16x2 tmin = w16(mint, mint), tini = w16(ini, ini);
+        struct Sel { uint32_t s01, s23; };  // pixel pairs (0,1) / (2,3) of the four bytes at s
+        auto sel = [&](int off) {
+            const int s = (off & 3) * 0x00010001;
+            return Sel{(uint32_t)uniform(0x0c010c00 + s), (uint32_t)uniform(0x0c030c02 + s)};
+        };
+        const Sel selL = sel(shift), selC = sel(shift + 3), selR = sel(shift + 6);
+        // bytes [8o + off .. +7] of an aligned row (off includes the row's shift) as four u16 pairs
+        auto ext8 = [&](const uint32_t* row, int o, int off, const Sel& S, u16x2 (&p)[4]) {
             const int d = 2 * o + (off >> 2);
             const uint32_t w0 = row[d], w1 = row[d + 1], w2 = row[d + 2];
-            a = __builtin_amdgcn_alignbyte(w1, w0, off & 3);
-            b = __builtin_amdgcn_alignbyte(w2, w1, off & 3);
+            p[0] = as_u16x2(__builtin_amdgcn_perm(w1, w0, S.s01));
+            p[1] = as_u16x2(__builtin_amdgcn_perm(w1, w0, S.s23));
+            p[2] = as_u16x2(__builtin_amdgcn_perm(w2, w1, S.s01));
+            p[3] = as_u16x2(__builtin_amdgcn_perm(w2, w1, S.s23));
         };
-        auto lo16 = [](uint32_t v) { return as_u16x2(__builtin_amdgcn_perm(v, v, 0x0c010c00u)); };
-        auto hi16 = [](uint32_t v) { return as_u16x2(__builtin_amdgcn_perm(v, v, 0x0c030c02u)); };
         // The adjacent compass pairs are exactly the pairs of one vertical point {p0, p8} and one
         // horizontal point {p4, p12}, so the largest pairwise minimum is min(max(p0, p8), max(p4, p12))
         // and the smallest pairwise maximum is max(min(p0, p8), min(p4, p12)): 3 packed ops each.
@@ -857,129 +890,127 @@ __device__ __forceinline__ void fast_cell(const KernelGeom& g, const CellDesc& C
             const u16x2 dmin = __builtin_elementwise_max(__builtin_elementwise_min(p0, p8), __builtin_elementwise_min(p4, p12));
             // bright <=> bmax - v > t, dark <=> v - dmin > t (saturating differences of u16 values <= 255)
             const u16x2 m = __builtin_elementwise_max(__builtin_elementwise_sub_sat(bmax, v), __builtin_elementwise_sub_sat(v, dmin));
-            // 0 / 1 per pixel (pass <=> m - t, saturated, is non-zero): one v_pk_min_u16 (as written
-            // in C the compiler turns the min into two compares, two selects and a v_perm)
-            uint32_t r;
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(__builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(m, tt))), "v"(0x00010001u));
-            return r;
+            // 0 / 1 per pixel and threshold (pass <=> m - t, saturated, is non-zero): one v_pk_min_u16
+            // each (as written in C the compiler turns the min into two compares, two selects and a
+            // v_perm); minTh in bit 0 of each half, iniTh in bit 8
+            uint32_t a, b;
+            asm("v_pk_min_u16 %0, %1, %2" : "=v"(a) : "v"(__builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(m, tmin))), "v"(0x00010001u));
+            asm("v_pk_min_u16 %0, %1, %2" : "=v"(b) : "v"(__builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(m, tini))), "v"(0x00010001u));
+            return a | (b << 8);
         };
-        // pass2 results of pixels (0,1), (2,3), (4,5), (6,7) as 0/1 halves, shifted into one word whose
-        // low half holds the even pixels' bits and high half the odd ones': bit k = pixel k after
-        // folding the high half down by 15
-        auto octet_bits = [&](uint32_t C0, uint32_t D0, uint32_t R0, uint32_t U0, uint32_t L0, uint32_t C1,
-                              uint32_t D1, uint32_t R1, uint32_t U1, uint32_t L1) {
-            const uint32_t p01 = pass2(lo16(C0), lo16(D0), lo16(R0), lo16(U0), lo16(L0));
-            const uint32_t p23 = pass2(hi16(C0), hi16(D0), hi16(R0), hi16(U0), hi16(L0));
-            const uint32_t p45 = pass2(lo16(C1), lo16(D1), lo16(R1), lo16(U1), lo16(L1));
-            const uint32_t p67 = pass2(hi16(C1), hi16(D1), hi16(R1), hi16(U1), hi16(L1));
-            const uint32_t t = p01 | (p23 << 2) | (p45 << 4) | (p67 << 6);
-            return (t & 0xffu) | (t >> 15);
-        };
-        // item -> (row, octet): one division here, then a fixed (row, octet) step of 64 items per round
-        int r = lane / no, o = lane - (lane / no) * no;
-        const int dr = 64 / no, dq = 64 - dr * no;
-        for (int i0 = 0; i0 < nitems; i0 += 64) {
-            const int it = i0 + lane;
-            unsigned bits = 0;
-            if (it < nitems) {
+        int r = r0, o = o0;
+        for (int i0 = 0, k = 0; i0 < nitems; i0 += 64, ++k) {
+            unsigned both = 0;  // byte 0: the octet's pixels passing at minTh, byte 1: at iniTh
+            if (i0 + lane < nitems) {
                 const uint32_t* rc = wrow + (r + 3) * wsw;
-                uint32_t L0, L1, C0, C1, R0, R1, U0, U1, D0, D1;
-                ext8(rc, o, shift, L0, L1);
-                ext8(rc, o, shift + 3, C0, C1);
-                ext8(rc, o, shift + 6, R0, R1);
-                ext8(rc - 3 * wsw, o, shift + 3, U0, U1);
-                ext8(rc + 3 * wsw, o, shift + 3, D0, D1);
-                bits = octet_bits(C0, D0, R0, U0, L0, C1, D1, R1, U1, L1);
+                u16x2 pl[4], pc[4], pr[4], pu[4], pd[4];
+                ext8(rc, o, shift, selL, pl);
+                ext8(rc, o, shift + 3, selC, pc);
+                ext8(rc, o, shift + 6, selR, pr);
+                ext8(rc - 3 * wsw, o, shift + 3, selC, pu);
+                ext8(rc + 3 * wsw, o, shift + 3, selC, pd);
+                // pass2 results of pixels (0,1), (2,3), (4,5), (6,7), shifted into one word whose low half
+                // holds the even pixels' bits and high half the odd ones': bit k (8 + k) = pixel k at
+                // minTh (iniTh) after folding the high half down by 15
+                const uint32_t t = pass2(pc[0], pd[0], pr[0], pu[0], pl[0]) | (pass2(pc[1], pd[1], pr[1], pu[1], pl[1]) << 2) |
+                                   (pass2(pc[2], pd[2], pr[2], pu[2], pl[2]) << 4) | (pass2(pc[3], pd[3], pr[3], pu[3], pl[3]) << 6);
+                both = (t | (t >> 15)) & 0xffffu;
                 const int rem = dw - 8 * o;  // pixels of this octet inside the detectable row
-                if (rem < 8) bits &= (1u << rem) - 1u;
+                if (rem < 8) both &= 0x0101u * ((1u << rem) - 1u);
             }
-            const int row = r, oct = o;
-            o += dq;
-            r += dr;
-            if (o >= no) { o -= no; ++r; }
-            const int cnt = __popc(bits);
-            const int incl = wave_incl_scan_dpp(cnt);
-            int pos = nlist + incl - cnt;
-            const int base_idx = ((row + 3) << 7) + 8 * oct + 3;  // (row << 7 | column), window coordinates
-            while (bits) {
-                const int k = __builtin_ctz(bits);
-                bits &= bits - 1u;
-                cl[pos++] = (uint16_t)(base_idx + k);
-            }
-            nlist += __builtin_amdgcn_readlane(incl, 63);
+#pragma unroll
+            for (int q = 0; q < kParkWords; ++q)
+                if (kParkWords == 1 || (k >> 2) == q) parked[q] |= (both & 0xffu) << (8 * (k & 3));
+            append(both >> 8, r, o);
+            next_item(r, o);
         }
     }
     wave_sync();
     FAST_STAMP(2);
-    // 1b. exact score of the filtered pixels: score >= minTh <=> a 9-arc corner at minTh (see
-    //     fast_score), so one pass both tests and scores; corners are compacted in place (row-major
-    //     order kept: every lane reads its entry before any lane writes, and writes land below j0 + 64)
-    //     and their scores go to the map
-    int ncand = 0;
-    for (int j0 = 0; j0 < nlist; j0 += 64) {
-        const int j = j0 + lane;
-        int idx = 0, s = -1;
-        if (j < nlist) {
-            idx = cl[j];
-            s = fast_score(win + (idx >> 7) * ws + (idx & 127), off);
-        }
-        const bool is_c = s >= mint;
-        const unsigned long long m = ballot(is_c);
-        if (is_c) {
-            cl[ncand + rank_in(m)] = (uint16_t)idx;
-            sc[sc_at(idx)] = (uint8_t)min(s, 255);
-        }
-        ncand += __popcll(m);
-    }
-    wave_sync();
-    FAST_STAMP(3);
-    FAST_STAMP(4);
-    // 3. iniTh first; minTh only if the cell has no corner at iniTh (src:1135-1148).  The local-maximum
-    //    test does not depend on the threshold: its result (score + 1, or 0) is kept per candidate in
-    //    the window's pixel buffer, which is free once the scores exist.
-    uint8_t* lmv = win - shift;
-    bool any = false;
-    for (int j = lane; j < ncand; j += 64) {
-        const int si = sc_at(cl[j]), s = sc[si];
-        const bool lm = is_local_max(sc, ss, si, s);
-        lmv[j] = lm ? (uint8_t)(s + 1) : (uint8_t)0;  // s <= 254 for a corner (9-arc minimum - 1)
-        any |= (s >= ini) && lm;
-    }
-    const int t = ballot(any) ? ini : mint;
-    wave_sync();
-    FAST_STAMP(5);
-    // 4. emission in row-major order (the candidate list is row-major)
+    // 2. iniTh first; minTh only if the cell yields no keypoint at iniTh (src:1135-1148).  When it
+    //    does, a pixel with score < iniTh can neither be emitted nor beat an emitted neighbour, so only
+    //    the iniTh list is scored.  Otherwise the scores written so far are cleared, the parked minTh
+    //    bits become the list, and the same passes run again at minTh.
     uint32_t* out = cand + (size_t)f * g.cand_frame_cap + L.cand_off + C.slot;
-    int count = 0;
-    for (int j0 = 0; j0 < ncand; j0 += 64) {
-        const int j = j0 + lane;
-        bool keep = false;
-        int idx = 0, s = 0;
-        if (j < ncand) {
-            idx = cl[j];
-            const int lv = lmv[j];
-            s = lv - 1;
-            keep = lv > 0 && s >= t;
+    int t = ini, count = 0, ncand = 0, scored = 0, rounds = 0;
+    for (;;) {
+        // 2a. exact score of the listed pixels: score >= t <=> a 9-arc corner at t (see fast_score), so
+        //     one pass both tests and scores; corners are compacted in place (row-major order kept:
+        //     every lane reads its entry before any lane writes, and writes land below j0 + 64) and
+        //     their scores go to the map
+        ncand = 0;
+        for (int j0 = 0; j0 < nlist; j0 += 64) {
+            const int j = j0 + lane;
+            int idx = 0, s = -1;
+            if (j < nlist) {
+                idx = cl[j];
+                s = fast_score(win + (idx >> 7) * ws + (idx & 127), off);
+            }
+            const bool is_c = s >= t;
+            const unsigned long long m = ballot(is_c);
+            if (is_c) {
+                cl[ncand + rank_in(m)] = (uint16_t)idx;
+                sc[sc_at(idx)] = (uint8_t)min(s, 255);
+            }
+            ncand += __popcll(m);
         }
-        const unsigned long long m = ballot(keep);
-        if (keep) {
-            const int pos = count + rank_in(m);
-            const int r = idx >> 7, c = idx & 127;
-            if (pos < C.cap) out[pos] = pack_key(C.off_x + c, C.off_y + r, s);
+        scored += nlist;
+        rounds += (nlist + 63) >> 6;
+        wave_sync();
+        FAST_STAMP(3);
+        // 2b. 3x3 local maxima among the corners, emitted in row-major order (the list is row-major)
+        count = 0;
+        for (int j0 = 0; j0 < ncand; j0 += 64) {
+            const int j = j0 + lane;
+            bool keep = false;
+            int idx = 0, s = 0;
+            if (j < ncand) {
+                idx = cl[j];
+                const int si = sc_at(idx);
+                s = sc[si];
+                keep = is_local_max(sc, ss, si, s);
+            }
+            const unsigned long long m = ballot(keep);
+            if (keep) {
+                const int pos = count + rank_in(m);
+                const int r = idx >> 7, c = idx & 127;
+                if (pos < C.cap) out[pos] = pack_key(C.off_x + c, C.off_y + r, s);
+            }
+            count += __popcll(m);
         }
-        count += __popcll(m);
+        if (count > 0 || t == mint) break;
+        // 2c. nothing survives at iniTh (no corner, or every corner ties with a neighbour)
+        wave_sync();
+        for (int j = lane; j < ncand; j += 64) sc[sc_at(cl[j])] = 0;
+        wave_sync();
+        nlist = 0;
+        int r = r0, o = o0;
+        for (int i0 = 0, k = 0; i0 < nitems; i0 += 64, ++k) {
+            unsigned bits = 0;
+#pragma unroll
+            for (int q = 0; q < kParkWords; ++q)
+                if (kParkWords == 1 || (k >> 2) == q) bits = (parked[q] >> (8 * (k & 3))) & 0xffu;
+            append(bits, r, o);
+            next_item(r, o);
+        }
+        wave_sync();
+        t = mint;
     }
     if (lane == 0) {
         cell_count[(size_t)f * g.ncells + cid] = min(count, (int)C.cap);
         cell_thr[(size_t)f * g.ncells + cid] = (uint8_t)t;
     }
-    if (stp && lane == 0) { stp[6] = __builtin_amdgcn_s_memtime(); stp[8] = wall_clock64(); stp[9] = nlist; stp[10] = ncand; }
+    if (stp && lane == 0) {
+        stp[4] = __builtin_amdgcn_s_memtime(); stp[8] = wall_clock64();
+        stp[5] = t != ini; stp[6] = rounds; stp[9] = scored; stp[10] = ncand;
+    }
 }
 
 
 // One wave per FAST cell.  LDS per wave: window | score map | candidate list (u16 pixel indices).
-// Pixels with score < minTh can neither be emitted nor beat an emitted neighbour, so the exact score
-// is computed only for the pixels that are corners at minTh (compacted list, no divergence).
+// Pixels with score < t can neither be emitted nor beat an emitted neighbour, so the exact score is
+// computed only for the pixels that pass the compass test at the threshold t the cell ends up using
+// (compacted list, no divergence): iniTh, or minTh for a cell that yields nothing at iniTh.
 __global__ __launch_bounds__(256) void k_fast_cells(const KernelGeom* __restrict__ gp, const CellDesc* __restrict__ cells, int win_cap, int sc_cap, int wave_lds,
                                                     const uint8_t* __restrict__ pyr, uint32_t* __restrict__ cand,
                                                     int32_t* __restrict__ cell_count, uint8_t* __restrict__ cell_thr,
@@ -995,8 +1026,9 @@ __global__ __launch_bounds__(256) void k_fast_cells(const KernelGeom* __restrict
     const int f = tb / groups;
     const int cid = cell0 + (tb - f * groups) * 4 + wave;
     if (cid >= cell_end) return;
-    // debug (ORBGPU_FAST_STAMPS): per-cell phase clocks of lane 0 (0 start .. 6 end, 7 wall start, 8 wall end,
-    // 9 survivors, 10 corners)
+    // debug (ORBGPU_FAST_STAMPS): per-cell phase clocks of lane 0 (0 start, 1 window staged, 2 compass,
+    // 3 scores of the last pass, 4 end), 5 minTh pass taken, 6 score rounds, 7 wall start, 8 wall end,
+    // 9 scored pixels (both passes), 10 corners at the threshold used
     unsigned long long* stp = stamps ? stamps + ((size_t)f * (cell_end - cell0) + (cid - cell0)) * 12 : nullptr;
     if (stp && lane == 0) { stp[7] = wall_clock64(); stp[0] = __builtin_amdgcn_s_memtime(); }
     const CellDesc C = cells[cid];
@@ -2514,22 +2546,24 @@ int launch_chunk(Extractor* e, int f0, const uint8_t* d_images, int n, int strid
             (void)hipStreamSynchronize(s2);
             (void)hipMemcpy(h.data(), stamps, ns * 8, hipMemcpyDeviceToHost);
             (void)hipFree(stamps);
-            double ph[6] = {0}, life = 0, sv = 0, cn = 0;
+            double ph[4] = {0}, life = 0, sv = 0, cn = 0, fb = 0, rd = 0;
             unsigned long long t0 = ~0ull, t1 = 0;
             size_t cnt = 0;
             for (size_t i = 0; i < ns; i += 12) {
                 if (!h[i + 7]) continue;
                 ++cnt;
-                for (int q = 1; q <= 6; ++q) ph[q - 1] += (double)(h[i + q] - h[i + q - 1]);
+                for (int q = 1; q <= 4; ++q) ph[q - 1] += (double)(h[i + q] - h[i + q - 1]);
+                fb += (double)h[i + 5];
+                rd += (double)h[i + 6];
                 life += (double)(h[i + 8] - h[i + 7]);
                 sv += (double)h[i + 9];
                 cn += (double)h[i + 10];
                 t0 = std::min(t0, h[i + 7]);
                 t1 = std::max(t1, h[i + 8]);
             }
-            fprintf(stderr, "fast-stamps L%d-%d cells %zu span %.1f us life %.2f us conc %.0f | stage %.0f compass %.0f full %.0f score %.0f thr %.0f emit %.0f cyc | surv %.1f corners %.1f\n",
+            fprintf(stderr, "fast-stamps L%d-%d cells %zu span %.1f us life %.2f us conc %.0f | stage %.0f compass %.0f score %.0f emit %.0f cyc | scored %.1f corners %.1f rounds %.3f minTh cells %.4f\n",
                     l0, l1 - 1, cnt, (t1 - t0) * 0.01, life / cnt * 0.01, life / (double)(t1 - t0), ph[0] / cnt, ph[1] / cnt,
-                    ph[2] / cnt, ph[3] / cnt, ph[4] / cnt, ph[5] / cnt, sv / cnt, cn / cnt);
+                    ph[2] / cnt, ph[3] / cnt, sv / cnt, cn / cnt, rd / cnt, fb / cnt);
         }
     };
     // quad-tree of levels [l0, l1): one wave per (level, frame)

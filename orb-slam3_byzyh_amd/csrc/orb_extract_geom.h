@@ -216,6 +216,7 @@ inline bool build_geometry(const Params& P, int width, int height, Geometry& g) 
                 g.max_win_lv[l] = std::max(g.max_win_lv[l], wbytes);
                 g.max_det_lv[l] = std::max(g.max_det_lv[l], dw * dh);
                 if (c.win_w >= 128 || c.win_h >= 512) return false;  // k_fast_cells' (row << 7 | column) entries
+                if ((dw + 7) / 8 * dh > 1024) return false;          // and its 16 rounds of parked compass octets
                 // score map: rows 2 .. win_h-3, columns 2 .. win_w-3, row stride 40 (win_w <= 44) or
                 // 48 (the fixed-stride kernel path), else win_w - 4 rounded up to a dword
                 const int ss = c.win_w <= 44 ? 40 : std::max(48, (c.win_w - 4 + 3) & ~3);
