@@ -256,6 +256,38 @@ int orb_search_for_triangulation_device(orb_matcher_t m, const orb_kf_device_t* 
                                         const orb_kf_pair_geom_t* geoms, int n_pairs, int only_stereo, int coarse,
                                         int32_t* d_matches12, int32_t* d_n_matches, void* stream);
 
+/* ---- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&) (src/ORBmatcher.cc:260-494) ----
+ * The matcher of Tracking::TrackReferenceKeyFrame (src/Tracking.cc:3943) and, once per candidate
+ * keyframe, of Tracking::Relocalization.  Single camera (F.Nleft == -1, mpCamera2 == NULL).  Only
+ * features under the same FeatureVector node are compared; inside a node the keyframe's features are
+ * visited in stored order, each taking its best frame feature among those no earlier one took (best /
+ * second best with strict `<` from 256 / -1 / 256, the first index on ties), accepted when
+ * bestDist1 <= TH_LOW and bestDist1 < mfNNratio * bestDist2; then, with mbCheckOrientation, the rotation
+ * histogram (factor 1 / HISTO_LENGTH as upstream has it) and ComputeThreeMaxima.  nnratio and
+ * check_orientation come from the handle.
+ *
+ * n_kfs keyframes against one frame in one launch (host memory, synchronous, through the handle's
+ * staging buffers and stream).  Of a view the search reads n, kps_un (the angle; mvKeys and mvKeysUn share
+ * it), desc and the three fv_* arrays, and of a keyframe its usable flags: point_ok[p][i] = 1 when
+ * pKF->GetMapPointMatches()[i] is non-NULL and not isBad() (point_ok or point_ok[p] NULL: the view's
+ * has_mappoint; that NULL too: no usable map point).  Writes matches[p * frame->n + iF] = the keyframe
+ * feature whose map point vpMapPointMatches[iF] receives, or -1, and n_matches[p] (the return value).  A
+ * view that lists a feature twice or an index >= n gives ORB_ERR_ARG. */
+int orb_search_by_bow(orb_matcher_t m, const orb_kf_view_t* kfs, const uint8_t* const* point_ok, int n_kfs,
+                      const orb_kf_view_t* frame, int32_t* matches, int32_t* n_matches);
+
+/* The same on device-resident sides (the orb_extract_batch_device / orb_bow_transform_frames_device
+ * layout of orb_kf_device_t, for the frames too), asynchronous on `stream`: pair p searches keyframe
+ * kfs[p] against frames[pair_frame[p]] (pair_frame NULL: frames[0]).  d_point_ok[p]: the keyframe's
+ * device flag array (cap entries; d_point_ok or the entry NULL: its has_mappoint).  Of a side the search
+ * reads kps, desc, n, the fv_* arrays, n_nodes and cap (< 2^20).  With C = max over frames of cap:
+ * d_matches[p * C + iF] (-1 past the frame's count), d_n_matches[p].  Counts are read on the device and
+ * clamped to cap; a side whose *n is negative or above cap, or whose *n_nodes is negative (flagged
+ * ORB_ERR_CAPACITY by its producer), gives d_n_matches[p] = ORB_ERR_CAPACITY and no matches. */
+int orb_search_by_bow_device(orb_matcher_t m, const orb_kf_device_t* kfs, const uint8_t* const* d_point_ok, int n_pairs,
+                             const orb_kf_device_t* frames, int n_frames, const int32_t* pair_frame,
+                             int32_t* d_matches, int32_t* d_n_matches, void* stream);
+
 /* ---- Frame::UndistortKeyPoints (src/Frame.cc:1003-1051): mvKeysUn from mvKeys by cv::undistortPoints
  * (OpenCV 4.x: five fixed-point iterations of the inverse k1 k2 p1 p2 k3 model in double, P = K, the
  * result rounded to float; parity with a real OpenCV build unpinned), on the extractor's device layout:
@@ -635,8 +667,8 @@ int orb_tracking_local_seen_device(const int32_t* d_match_a, int cap, int last_c
  * (src/Tracking.cc:4149-4217): fewer than 20 matches -> the search again with 2 th; still fewer than 20
  * -> TrackWithMotionModel returns false: no PoseOptimization, no local-map stages; after the first
  * PoseOptimization and the discard, nmatchesMap < 10 -> it returns false too and the local-map stages
- * are skipped (the reference's Track() then runs TrackReferenceKeyFrame, the caller's).  The per-frame
- * status word says which (ORB_TRACK_*).  For a frame that fails: m1 holds the last search's matches
+ * are skipped (the reference's Track() then runs TrackReferenceKeyFrame: orb_track_reference_kf_device
+ * below).  The per-frame status word says which (ORB_TRACK_*).  For a frame that fails: m1 holds the last search's matches
  * (status FAIL_SEARCH: not discarded, no graph: n_edges 0, pose1 = the motion model's pose) or the
  * discarded ones (FAIL_MAP); m2 is all -1 and n_match[1] 0; the second graph is empty and pose2 is the
  * pose the Frame keeps after TrackWithMotionModel (pose1 through Frame::SetPose's float round trip);
@@ -744,6 +776,43 @@ int orb_tracking_chain_batch_release(void* scratch);
 int orb_tracking_chain_batch_device(orb_matcher_t m_motion, orb_matcher_t m_local, int n_frames,
                                     const orb_tracking_chain_frame_t* frames, const orb_tracking_chain_params_t* params,
                                     const orb_tracking_chain_batch_buffers_t* bufs, void* stream);
+
+/* ---- Tracking::TrackReferenceKeyFrame (src/Tracking.cc:3931-4000) on device arrays, no host hop,
+ * asynchronous on `stream`: where Tracking::Track hands a frame the motion model could not track (the
+ * chain's ORB_TRACK_FAIL_SEARCH / ORB_TRACK_FAIL_MAP, the first frame after initialisation or a
+ * relocalisation).  The caller has run Frame::ComputeBoW (orb_bow_transform_frames_device).
+ *   SearchByBoW(mpReferenceKF, mCurrentFrame) with m = ORBmatcher(0.7, true)     -> match, n_match
+ *   nmatches < 15: returns false -- status ORB_TRACK_REF_FAIL_BOW, no graph (n_edges 0), pose = pose7, the
+ *     matches stay as the search left them, n_out 0 (a side flagged ORB_ERR_CAPACITY ends here too)
+ *   PoseOptimization from the last frame's pose (pose7, an input): orb_tracking_pose_edges_device with
+ *     d_match_a = match and d_xyz_a = d_xyz, then orb_pose_optimization_device         -> pose, outlier
+ *   the outlier discard (:3966-3994, orb_tracking_discard_outliers_device with d_observed)  -> match, n_out
+ *   nmatchesMap < 10 and not imu: status ORB_TRACK_REF_FAIL_MAP (imu: the IMU sensors return true, :3996)
+ * kf / d_point_ok: as orb_search_by_bow_device.  d_observed, d_xyz: per keyframe feature, its map point's
+ * Observations() > 0 (NULL: all) and GetWorldPos() (cap x 3).  frame_bow: the frame as SearchByBoW reads it;
+ * frame: the same frame as PoseOptimization reads it (mvKeysUn, mvuRight, camera; the same cap).  The
+ * status bits continue the ORB_TRACK_* word. */
+#define ORB_TRACK_REF_FAIL_BOW 8   /* SearchByBoW found < 15: TrackReferenceKeyFrame false */
+#define ORB_TRACK_REF_FAIL_MAP 16  /* nmatchesMap < 10 after PoseOptimization: TrackReferenceKeyFrame false */
+typedef struct orb_track_reference_kf_buffers {
+    int32_t* match;             /* cap: the keyframe feature whose map point keypoint i holds, after the discard */
+    int32_t* n_match;           /* 1: SearchByBoW's return */
+    orb_pose_frame_t* frame;    /* 1: the PoseOptimization graph's frame record */
+    orb_pose_edge_t* edges;     /* cap */
+    int32_t* edge_kp;           /* cap: keypoint of each edge */
+    uint8_t* outlier;           /* cap: mvbOutlier per edge */
+    double* pose;               /* 7: the optimised pose (SE3Quat vector) */
+    int32_t* inliers;           /* 1: PoseOptimization's return */
+    int32_t* n_out;             /* 2: nmatches after the discard, nmatchesMap */
+    void* scratch;              /* orb_track_reference_kf_scratch_bytes(cap) (required) */
+    int32_t* status;            /* 1: 0 (tracked) or an ORB_TRACK_REF_* bit; NULL: not reported */
+} orb_track_reference_kf_buffers_t;
+
+size_t orb_track_reference_kf_scratch_bytes(int cap);
+int orb_track_reference_kf_device(orb_matcher_t m, const orb_kf_device_t* kf, const uint8_t* d_point_ok,
+                                  const uint8_t* d_observed, const float* d_xyz, const orb_kf_device_t* frame_bow,
+                                  const orb_frame_device_t* frame, const float* inv_level_sigma2, const double pose7[7],
+                                  int imu, const orb_track_reference_kf_buffers_t* bufs, void* stream);
 
 /* ---- multi-GPU local BA: one process per GPU, every rank passes the same
  * problem; rank r owns a contiguous, edge-balanced range of the landmarks and their edges, and

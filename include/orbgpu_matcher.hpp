@@ -8,11 +8,12 @@
  *                                                                                (:1046-1324)
  *   int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)   (:1951-2185)
  *   int SearchByProjection(Frame& F, const vector<MapPoint*>&, th, bFarPoints, thFarPoints) (:46-240)
+ *   int SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)   (:260-494)
  *
  * The class translates the reference's KeyFrame / Frame / MapPoint objects into the ABI's flat views
  * (orb_kf_view_t, orb_frame_view_t, orb_last_points_t, orb_local_points_t), calls the HIP matcher,
  * and writes the results back exactly where the reference writes them (vMatchedPairs,
- * CurrentFrame.mvpMapPoints, F.mvpMapPoints).  The object graph is reached through an accessor type A
+ * CurrentFrame.mvpMapPoints, F.mvpMapPoints, vpMapPointMatches).  The object graph is reached through an accessor type A
  * so that the same code runs on the reference's classes (orbgpu::ORBSLAM3MatcherAccess below, compiled
  * inside the reference build) and on a mock graph in this repository's CPU test
  * (tests/native/matcher_shim_check.cpp):
@@ -35,6 +36,8 @@
  *     static std::vector<MapPoint*>& MapPoints(Frame&); // mvpMapPoints
  *     static const std::vector<MapPoint*>& MapPoints(const Frame&);
  *     static bool Outlier(const Frame&, int i);         // mvbOutlier[i]
+ *     static const FeatureVector& FeatVec(const Frame&);  // mFeatVec after Frame::ComputeBoW (SearchByBoW only;
+ *                                                       // it reads the frame's keypoints and descriptors from View)
  *     // map points
  *     static int Observations(MapPoint*);  static bool IsBad(MapPoint*);
  *     static void WorldPos(MapPoint*, float X[3]);  static void Descriptor(MapPoint*, uint8_t d[32]);
@@ -46,7 +49,8 @@
  * reference's CPU body.
  *
  * Failures (orbgpu_status.hpp): nothing here throws.  A library failure returns the reference's result
- * for a search that matches nothing -- 0, vMatchedPairs empty, no map point written -- and a failed
+ * for a search that matches nothing -- 0, vMatchedPairs empty, no map point written (SearchByBoW: every
+ * entry of vpMapPointMatches NULL) -- and a failed
  * ComputeDistinctiveDescriptors leaves every descriptor as it was; orbgpu::LastShimError() reports it.
  */
 #ifndef ORBGPU_MATCHER_HPP
@@ -105,6 +109,21 @@ inline orb_matcher_t ThreadHandle(float nnratio, bool check_ori) {
     return cache.Get(nnratio, check_ori);
 }
 
+// A DBoW2::FeatureVector (std::map: node ids ascending, each node's indices in insertion order) as the
+// views' CSR arrays.
+template <class FV>
+inline void FlattenFeatVec(const FV& fv, std::vector<uint32_t>& node, std::vector<int32_t>& offset,
+                           std::vector<int32_t>& index) {
+    node.reserve(fv.size());
+    offset.reserve(fv.size() + 1);
+    offset.push_back(0);
+    for (const auto& kv : fv) {
+        node.push_back((uint32_t)kv.first);
+        for (auto idx : kv.second) index.push_back((int32_t)idx);
+        offset.push_back((int32_t)index.size());
+    }
+}
+
 // A keyframe's orb_kf_view_t and the arrays it points into.
 template <class A>
 struct KfViewStore {
@@ -118,15 +137,7 @@ struct KfViewStore {
         const auto mps = A::MapPointMatches(k);
         has_mp.resize(n);
         for (int i = 0; i < n; ++i) has_mp[i] = (i < (int)mps.size() && mps[i]) ? 1 : 0;  // GetMapPoint(i) != NULL
-        const auto& fv = A::FeatVec(k);
-        node.reserve(fv.size());
-        offset.reserve(fv.size() + 1);
-        offset.push_back(0);
-        for (const auto& kv : fv) {  // std::map: node ids ascending, each node's indices in insertion order
-            node.push_back((uint32_t)kv.first);
-            for (auto idx : kv.second) index.push_back((int32_t)idx);
-            offset.push_back((int32_t)index.size());
-        }
+        FlattenFeatVec(A::FeatVec(k), node, offset, index);
         float K[4];
         A::Pinhole(k, K);
         view.n = n;
@@ -168,6 +179,7 @@ public:
 
     static bool Supports(KeyFrame* a, KeyFrame* b) { return A::SingleCamera(a) && A::SingleCamera(b); }
     static bool Supports(const Frame& f) { return A::SingleCamera(f); }
+    static bool Supports(KeyFrame* k, const Frame& f) { return A::SingleCamera(k) && A::SingleCamera(f); }
 
     // src/ORBmatcher.cc:1046-1324.  vMatchedPairs = (idx1, idx2) in increasing idx1 (:1313-1321).
     int SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<std::pair<size_t, size_t>>& vMatchedPairs,
@@ -312,6 +324,40 @@ public:
         return n;
     }
 
+    // src/ORBmatcher.cc:260-494 (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:3943; Relocalization's
+    // candidate loop).  vpMapPointMatches is set to F.N NULL entries first (:266); entry i then receives
+    // pKF's map point of the keyframe feature matched to keypoint i.  F.mFeatVec must be computed
+    // (Frame::ComputeBoW, as both callers do before the search).
+    int SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches) {
+        const std::vector<MapPoint*> vpMapPointsKF = A::MapPointMatches(pKF);
+        const orb_frame_view_t fv = A::View(F);
+        const int nf = fv.n > 0 ? fv.n : 0;
+        vpMapPointMatches.assign(nf, static_cast<MapPoint*>(nullptr));
+        detail::KfViewStore<A> kv(pKF);
+        std::vector<uint8_t> usable(kv.view.n > 0 ? kv.view.n : 1, 0);
+        for (int i = 0; i < kv.view.n && i < (int)vpMapPointsKF.size(); ++i)  // pMP && !pMP->isBad() (:307-313)
+            usable[i] = (vpMapPointsKF[i] && !A::IsBad(vpMapPointsKF[i])) ? 1 : 0;
+        std::vector<uint32_t> node;
+        std::vector<int32_t> offset, index;
+        detail::FlattenFeatVec(A::FeatVec(static_cast<const Frame&>(F)), node, offset, index);
+        orb_kf_view_t frame{};  // what a search reads of the frame: n, keypoints (angle), descriptors, FeatureVector
+        frame.n = nf;
+        frame.kps_un = fv.kps_un;
+        frame.desc = fv.desc;
+        frame.n_nodes = (int32_t)node.size();
+        frame.fv_node = node.data();
+        frame.fv_offset = offset.data();
+        frame.fv_index = index.data();
+        const uint8_t* flags = usable.data();
+        std::vector<int32_t> match(nf > 0 ? nf : 1, -1);
+        int32_t n = 0;
+        if (Failed(orb_search_by_bow(Handle(), &kv.view, &flags, 1, &frame, match.data(), &n), "orb_search_by_bow"))
+            return 0;  // every entry NULL
+        for (int i = 0; i < nf; ++i)
+            if (match[i] >= 0) vpMapPointMatches[i] = vpMapPointsKF[match[i]];  // vpMapPointMatches[bestIdxF] = pMP (:391)
+        return n;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -426,6 +472,7 @@ struct ORBSLAM3MatcherAccess {
     static std::vector<MapPoint*>& MapPoints(Frame& f) { return f.mvpMapPoints; }
     static const std::vector<MapPoint*>& MapPoints(const Frame& f) { return f.mvpMapPoints; }
     static bool Outlier(const Frame& f, int i) { return f.mvbOutlier[i]; }
+    static const DBoW2::FeatureVector& FeatVec(const Frame& f) { return f.mFeatVec; }
 
     static int Observations(MapPoint* p) { return p->Observations(); }
     static bool IsBad(MapPoint* p) { return p->isBad(); }

@@ -101,6 +101,8 @@ PROTOTYPES = {
     "orb_kf_pair_geometry": (_i, [_vp, _vp, _f, _f, _f, _f, _vp]),
     "orb_search_for_triangulation": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "orb_search_for_triangulation_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "orb_search_by_bow": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "orb_search_by_bow_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "orb_search_by_projection_frame": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp]),
     "orb_search_by_projection_local": (_i, [_vp, _vp, _vp, _vp, _f, _i, _f, _vp, _vp]),
     "orb_compute_stereo_matches": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp]),
@@ -128,6 +130,8 @@ PROTOTYPES = {
     "orb_tracking_chain_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "orb_tracking_chain_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
+    "orb_track_reference_kf_scratch_bytes": (_sz, [_i]),
+    "orb_track_reference_kf_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "orb_ba_create": (_i, [ctypes.POINTER(_vp)]),
     "orb_ba_destroy": (_i, [_vp]),
     "orb_ba_optimize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -24,12 +24,13 @@
 #include <cstdlib>
 
 #include "orbgpu.h"
+#include "orb_rot_hist.h"
 #include "orbgpu_internal.h"
 
 namespace {
 
 constexpr int kGridCols = 64, kGridRows = 48;  // include/Frame.h:44-45
-constexpr int kThHigh = 100, kHisto = 30;
+constexpr int kThHigh = 100, kHisto = kOrbHistoLength;
 constexpr int kMaxLevels = 12;
 
 struct ProjParams {
@@ -329,13 +330,7 @@ __global__ __launch_bounds__(kCandThreads) void k_proj_candidates_t_b(const k_pr
                              A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.lister);
 }
 
-__device__ __forceinline__ int rot_bin(float a1, float a2) {
-    float rot = a1 - a2;
-    if ((double)rot < 0.0) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / kHisto));
-    if (bin == kHisto) bin = 0;
-    return bin;
-}
+__device__ __forceinline__ int rot_bin(float a1, float a2) { return orb_rot_bin(a1, a2); }
 
 // ---- SearchByProjection(Frame&, vector<MapPoint*>, th, bFarPoints, thFarPoints), src:46-240 -------
 
@@ -919,18 +914,7 @@ __device__ __forceinline__ void k_resolve_rounds_body(ResolveArgs a) {
     atomicAdd(&cnt[0], nsucc);
     __syncthreads();
     if (a.check_ori) {
-        if (tid == 0) {  // ComputeThreeMaxima (src:2336-2378)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < kHisto; ++b) {
-                const int s = hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
+        if (tid == 0) orb_three_maxima(hist, keep);  // ComputeThreeMaxima (src:2336-2378)
         __syncthreads();
         int nrem = 0;
         for (int i = tid; i < a.n_pts; i += kResolveThreads) {

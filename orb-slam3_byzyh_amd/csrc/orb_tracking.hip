@@ -18,6 +18,9 @@
 //                         match and no edge, so a failed frame's remaining launches do no work and
 //                         write the "not run" outputs, with no host round trip and no change to the
 //                         stage kernels.
+//   k_track_ref_gate_*    Tracking::TrackReferenceKeyFrame's decisions (src/Tracking.cc:3946-3950, 3996-3999)
+//                         for orb_track_reference_kf_device (SearchByBoW -> PoseOptimization -> discard), the
+//                         same way: fewer than 15 matches -> an empty graph, nmatchesMap < 10 -> failure.
 // Map points are referenced by index into a device table of world positions (float xyz, as
 // MapPoint::GetWorldPos returns them); a keypoint's map point comes from the second match array when it
 // has one there (SearchByProjection(F, local points) overwrites, src/ORBmatcher.cc:156), else the first.
@@ -362,6 +365,32 @@ __global__ __launch_bounds__(kThreads) void k_track_gate_map_b(const GateArgs* _
     k_track_gate_map_body(a[blockIdx.y]);
 }
 
+// ---- TrackReferenceKeyFrame's decisions (src/Tracking.cc:3946-3950, 3996-3999)
+constexpr int kMinBowMatches = 15;  // nmatches < 15: TrackReferenceKeyFrame returns false (:3946)
+
+struct RefGate {
+    int32_t n_alive;  // PoseOptimization's graph / the discard: N unless SearchByBoW found too few
+    int32_t status;   // ORB_TRACK_REF_* bits
+};
+
+// after SearchByBoW: < 15 matches (or a side flagged ORB_ERR_CAPACITY) -> no graph
+__global__ __launch_bounds__(64) void k_track_ref_gate_bow(RefGate* g, const int32_t* __restrict__ n_match,
+                                                           const int32_t* __restrict__ cur_n, int32_t* status) {
+    if (threadIdx.x) return;
+    const bool ok = *n_match >= kMinBowMatches;
+    g->n_alive = ok ? *cur_n : 0;
+    g->status = ok ? 0 : ORB_TRACK_REF_FAIL_BOW;
+    if (status) *status = g->status;
+}
+// after the discard: nmatchesMap < 10 -> false, unless an IMU sensor tracks (:3996-3999)
+__global__ __launch_bounds__(64) void k_track_ref_gate_map(RefGate* g, const int32_t* __restrict__ n_out, int imu,
+                                                           int32_t* status) {
+    if (threadIdx.x) return;
+    if (!(g->status & ORB_TRACK_REF_FAIL_BOW) && !imu && n_out[1] < kMinMapMatches)
+        g->status |= ORB_TRACK_REF_FAIL_MAP;
+    if (status) *status = g->status;
+}
+
 // A frame view whose keypoint count is read from `n` (a gate word) instead of the frame's own
 __host__ orb_frame_device_t gated(const orb_frame_device_t* F, const int32_t* n) {
     orb_frame_device_t G = *F;
@@ -526,6 +555,42 @@ int orb_tracking_chain_device(orb_matcher_t m_motion, orb_matcher_t m_local, con
         return rc;
     return orbgpu_pose_optimization_device_scratch(1, B->frames + 1, F->cap, B->edges2, B->poses + 7, B->outlier2,
                                                    B->inliers + 1, stream, static_cast<double*>(z));
+}
+
+size_t orb_track_reference_kf_scratch_bytes(int cap) {
+    if (cap <= 0) return 0;
+    return (((size_t)cap * sizeof(double) + 255) & ~(size_t)255) + 256;  // PoseOptimization's chi2 | the gate record
+}
+
+int orb_track_reference_kf_device(orb_matcher_t m, const orb_kf_device_t* kf, const uint8_t* d_point_ok,
+                                  const uint8_t* d_observed, const float* d_xyz, const orb_kf_device_t* frame_bow,
+                                  const orb_frame_device_t* F, const float* inv_level_sigma2, const double pose7[7],
+                                  int imu, const orb_track_reference_kf_buffers_t* B, void* stream) {
+    if (!m || !kf || !d_xyz || !frame_bow || !F || !inv_level_sigma2 || !pose7 || !B || !B->match || !B->n_match ||
+        !B->frame || !B->edges || !B->edge_kp || !B->outlier || !B->pose || !B->inliers || !B->n_out || !B->scratch ||
+        F->cap <= 0 || F->cap != frame_bow->cap || !F->n)
+        return orbgpu_fail(ORB_ERR_ARG, "bad TrackReferenceKeyFrame arguments (frame and frame_bow share cap)");
+    hipStream_t s = (hipStream_t)stream;
+    double* const chi = static_cast<double*>(B->scratch);
+    RefGate* const g = reinterpret_cast<RefGate*>(static_cast<char*>(B->scratch) +
+                                                  (((size_t)F->cap * sizeof(double) + 255) & ~(size_t)255));
+    int rc;
+    if ((rc = orb_search_by_bow_device(m, kf, &d_point_ok, 1, frame_bow, 1, nullptr, B->match, B->n_match, stream)))
+        return rc;
+    hipLaunchKernelGGL(k_track_ref_gate_bow, dim3(1), dim3(64), 0, s, g, B->n_match, F->n, B->status);
+    const orb_frame_device_t F1 = gated(F, &g->n_alive);
+    if ((rc = orb_tracking_pose_edges_device(&F1, B->match, d_xyz, nullptr, nullptr, inv_level_sigma2, nullptr, pose7,
+                                             B->frame, B->edges, B->edge_kp, stream)))
+        return rc;
+    if ((rc = orbgpu_pose_optimization_device_scratch(1, B->frame, F->cap, B->edges, B->pose, B->outlier, B->inliers,
+                                                      stream, chi)))
+        return rc;
+    if ((rc = orb_tracking_discard_outliers_device(B->frame, B->edge_kp, B->outlier, B->match, d_observed, nullptr,
+                                                   nullptr, B->n_out, F->cap, nullptr, stream)))
+        return rc;
+    hipLaunchKernelGGL(k_track_ref_gate_map, dim3(1), dim3(64), 0, s, g, B->n_out, imu ? 1 : 0, B->status);
+    if (hipGetLastError() != hipSuccess) return orbgpu_fail(ORB_ERR_DEVICE, "TrackReferenceKeyFrame launch failed");
+    return ORB_OK;
 }
 
 size_t orb_tracking_chain_batch_scratch_bytes(int n_frames, int cap, int last_cap, int n_local) {

@@ -25,12 +25,13 @@
 #include <vector>
 
 #include "orbgpu.h"
+#include "orb_rot_hist.h"
 #include "orbgpu_internal.h"
 
 namespace {
 
 constexpr int kThLow = 50;        // src/ORBmatcher.cc:37
-constexpr int kHistoLength = 30;  // src/ORBmatcher.cc:38
+constexpr int kHistoLength = kOrbHistoLength;  // src/ORBmatcher.cc:38
 constexpr int kMaxLevels = 12;
 constexpr int kWaves = 4;
 
@@ -198,14 +199,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_tri_match(Src src, const PairDe
     }
 }
 
-__device__ __forceinline__ int rot_bin(float a1, float a2) {
-    float rot = a1 - a2;  // src:1262-1266
-    if ((double)rot < 0.0) rot += 360.0f;
-    const float factor = 1.0f / kHistoLength;  // the reference's factor (src:1099), kept as is
-    int bin = (int)roundf(rot * factor);
-    if (bin == kHistoLength) bin = 0;
-    return bin;
-}
+__device__ __forceinline__ int rot_bin(float a1, float a2) { return orb_rot_bin(a1, a2); }  // src:1262-1266
 
 template <class Src>
 __global__ __launch_bounds__(256) void k_tri_finish(Src src, const int32_t* __restrict__ k1of, int k2base, int check_ori,
@@ -237,24 +231,7 @@ __global__ __launch_bounds__(256) void k_tri_finish(Src src, const int32_t* __re
     }
     if (check_ori) {
         __syncthreads();
-        if (threadIdx.x == 0) {  // ComputeThreeMaxima (src:2336-2378)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < kHistoLength; ++i) {
-                const int s = hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    ind3 = ind2; ind2 = ind1; ind1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    ind3 = ind2; ind2 = i;
-                } else if (s > max3) {
-                    max3 = s; ind3 = i;
-                }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) ind3 = -1;
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
+        if (threadIdx.x == 0) orb_three_maxima(hist, keep);  // ComputeThreeMaxima (src:2336-2378)
         __syncthreads();
         for (int i = threadIdx.x; i < n1; i += blockDim.x) {
             const int j = m[i];
@@ -396,6 +373,27 @@ int orbgpu_matcher_reserve(orb_matcher_t m, size_t bytes, char** d_buf, char** h
     *stream = m->stream;
     *check_ori = m->check_ori;
     return ORB_OK;
+}
+
+// The pinned upload slot of the device-resident entry points: waits until the previous call's upload
+// has left it, grows it to `bytes`; orbgpu_matcher_upload_mark records the end of this call's copy.
+int orbgpu_matcher_upload_slot(orb_matcher_t m, size_t bytes, char** h) {
+    if (!m->dev_ev && hipEventCreateWithFlags(&m->dev_ev, hipEventDisableTiming) != hipSuccess)
+        return orbgpu_fail(ORB_ERR_DEVICE, "event create");
+    if (hipEventSynchronize(m->dev_ev) != hipSuccess) return orbgpu_fail(ORB_ERR_DEVICE, "device error");
+    if (bytes > m->h_dev_cap) {
+        if (m->h_dev) hipHostFree(m->h_dev);
+        m->h_dev = nullptr;
+        m->h_dev_cap = 0;
+        if (hipHostMalloc(&m->h_dev, bytes, hipHostMallocDefault) != hipSuccess)
+            return orbgpu_fail(ORB_ERR_DEVICE, "matcher pinned alloc");
+        m->h_dev_cap = bytes;
+    }
+    *h = m->h_dev;
+    return ORB_OK;
+}
+int orbgpu_matcher_upload_mark(orb_matcher_t m, hipStream_t s) {
+    return hipEventRecord(m->dev_ev, s) == hipSuccess ? ORB_OK : ORB_ERR_DEVICE;
 }
 
 float orbgpu_matcher_nnratio(orb_matcher_t m) { return m->nnratio; }
@@ -581,21 +579,11 @@ int orb_search_for_triangulation_device(orb_matcher_t m, const orb_kf_device_t* 
     // upload: KfPtrs [n_kf1 first keyframes | n_pairs neighbours] | PairDev [n_pairs] | kf1 index per pair
     const size_t o_pair = align256(nkf * sizeof(KfPtrs)), o_k1 = o_pair + align256(n_pairs * sizeof(PairDev));
     const size_t bytes = o_k1 + align256(4 * (size_t)n_pairs);
-    // the pinned slot: wait until the previous call's upload has left it
-    if (!m->dev_ev && hipEventCreateWithFlags(&m->dev_ev, hipEventDisableTiming) != hipSuccess)
-        return orbgpu_fail(ORB_ERR_DEVICE, "event create");
-    if (hipEventSynchronize(m->dev_ev) != hipSuccess) return orbgpu_fail(ORB_ERR_DEVICE, "device error");
-    if (bytes > m->h_dev_cap) {
-        if (m->h_dev) hipHostFree(m->h_dev);
-        m->h_dev = nullptr;
-        m->h_dev_cap = 0;
-        if (hipHostMalloc(&m->h_dev, bytes, hipHostMallocDefault) != hipSuccess)
-            return orbgpu_fail(ORB_ERR_DEVICE, "matcher pinned alloc");
-        m->h_dev_cap = bytes;
-    }
-    auto* kp = reinterpret_cast<KfPtrs*>(m->h_dev);
-    auto* pd = reinterpret_cast<PairDev*>(m->h_dev + o_pair);
-    auto* k1 = reinterpret_cast<int32_t*>(m->h_dev + o_k1);
+    char* h_dev = nullptr;
+    if (int rc = orbgpu_matcher_upload_slot(m, bytes, &h_dev)) return rc;
+    auto* kp = reinterpret_cast<KfPtrs*>(h_dev);
+    auto* pd = reinterpret_cast<PairDev*>(h_dev + o_pair);
+    auto* k1 = reinterpret_cast<int32_t*>(h_dev + o_k1);
     for (int k = 0; k < nkf; ++k) {
         const orb_kf_device_t& v = k < n_kf1 ? kf1s[k] : kf2s[k - n_kf1];
         kp[k] = KfPtrs{v.kps, reinterpret_cast<const uint4*>(v.desc), v.n, v.u_right, v.has_mappoint, v.fv_node,
@@ -612,8 +600,8 @@ int orb_search_for_triangulation_device(orb_matcher_t m, const orb_kf_device_t* 
     char* d = nullptr;
     if (hipMallocAsync(reinterpret_cast<void**>(&d), bytes, s) != hipSuccess)
         return orbgpu_fail(ORB_ERR_DEVICE, "hipMallocAsync failed");
-    bool ok = hipMemcpyAsync(d, m->h_dev, bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
-              hipEventRecord(m->dev_ev, s) == hipSuccess &&
+    bool ok = hipMemcpyAsync(d, h_dev, bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+              orbgpu_matcher_upload_mark(m, s) == ORB_OK &&
               hipMemsetAsync(d_matches12, 0xFF, (size_t)n_pairs * C * 4, s) == hipSuccess;
     const DirectSrc src{reinterpret_cast<const KfPtrs*>(d)};
     const int32_t* k1of = reinterpret_cast<const int32_t*>(d + o_k1);

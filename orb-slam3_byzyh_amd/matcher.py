@@ -116,6 +116,61 @@ class ORBmatcher:
         C = max(g[0].cap for g in groups)
         return kf1v, n1, kf2v, k1, geoms, n_pairs, C, groups[0][0]._keep[0].device
 
+    def SearchByBoW(self, pKF: KeyFrame, F: KeyFrame, point_ok=None):
+        """SearchByBoW(KeyFrame *pKF, Frame &F, vector<MapPoint*> &vpMapPointMatches) (src/ORBmatcher.cc:260-494),
+        single camera.  F: the frame as a KeyFrame-shaped view (keypoints, descriptors, mFeatVec).  point_ok[i]:
+        pKF's map point i is non-NULL and not isBad() (None: pKF.has_mappoint).  Returns (nmatches, match
+        int32[F.N]) with match[iF] = the feature of pKF whose map point vpMapPointMatches[iF] receives (-1: NULL)."""
+        (n, m), = self.SearchByBoWMany([pKF], F, None if point_ok is None else [point_ok])
+        return n, m
+
+    def SearchByBoWMany(self, kfs, F: KeyFrame, point_ok=None):
+        """SearchByBoW of every keyframe in `kfs` against F in one device launch (the candidate loop of
+        Tracking::Relocalization).  point_ok: per keyframe a flag array or None.  Returns [(nmatches, match)]."""
+        kfs = list(kfs)
+        p = len(kfs)
+        if p == 0:
+            return []
+        views = (KfView * p)(*[k.view() for k in kfs])
+        oks = [None] * p if point_ok is None else [None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+                                                   for a in point_ok]
+        if len(oks) != p or any(a is not None and len(a) != k.N for a, k in zip(oks, kfs)):
+            raise ValueError("point_ok: one array of pKF.N flags (or None) per keyframe")
+        okp = (ctypes.c_void_p * p)(*[None if a is None else a.ctypes.data for a in oks])
+        m = np.full((p, max(F.N, 1)), -1, np.int32)
+        cnt = np.zeros(p, np.int32)
+        check(_lib.load().orb_search_by_bow(self._handle(), views, okp, p, ctypes.byref(F.view()), m.ctypes.data,
+                                            cnt.ctypes.data), "orb_search_by_bow")
+        return [(int(cnt[i]), m[i, :F.N]) for i in range(p)]
+
+    def SearchByBoWDevice(self, kfs, frames, point_ok=None, pair_frame=None, stream=None, out=None):
+        """SearchByBoW on device-resident sides (orb_search_by_bow_device): pair p matches the DeviceKeyFrame
+        kfs[p] against frames[pair_frame[p]] (a single DeviceKeyFrame or a list; pair_frame None: frames[0]).
+        point_ok: per keyframe a uint8 CUDA tensor of cap flags or None (the keyframe's has_mappoint).
+        Returns (match [P, C] int32, counts [P] int32) CUDA tensors, C = max cap of the frames; a side
+        flagged ORB_ERR_CAPACITY gives that count.  Asynchronous on `stream`."""
+        import torch
+        kfs = list(kfs)
+        frames = [frames] if isinstance(frames, DeviceKeyFrame) else list(frames)
+        p, nf = len(kfs), len(frames)
+        dev = frames[0]._keep[0].device
+        C = max(f.cap for f in frames)
+        if out is None:
+            out = (torch.empty((max(p, 1), C), dtype=torch.int32, device=dev),
+                   torch.empty(max(p, 1), dtype=torch.int32, device=dev))
+        if p == 0:
+            return out
+        kv = (KfDeviceView * p)(*[k.view() for k in kfs])
+        fv = (KfDeviceView * nf)(*[f.view() for f in frames])
+        oks = [None] * p if point_ok is None else list(point_ok)
+        okp = (ctypes.c_void_p * p)(*[None if a is None else a.data_ptr() for a in oks])
+        pf = None if pair_frame is None else (ctypes.c_int32 * p)(*[int(i) for i in pair_frame])
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        check(_lib.load().orb_search_by_bow_device(self._handle(), kv, okp, p, fv, nf, pf, out[0].data_ptr(),
+                                                   out[1].data_ptr(), ctypes.c_void_p(st.cuda_stream)),
+              "orb_search_by_bow_device")
+        return out
+
     @staticmethod
     def DescriptorDistance(a, b) -> int:
         """Hamming distance of two 32-byte descriptors (src/ORBmatcher.cc:2384-2404)."""

@@ -20,7 +20,16 @@ TrackWithMotionModel's decisions run on the device too (gate=True, src/Tracking.
 than 20 matches -> the search again with 2 th; still fewer -> the frame fails (no PoseOptimization,
 no local-map stages); nmatchesMap < 10 after the first PoseOptimization -> it fails as well.  The
 result's `status` holds the ORB_TRACK_* bits (RETRIED 1, FAIL_SEARCH 2, FAIL_MAP 4); a failed frame is
-the caller's to hand to TrackReferenceKeyFrame, as Tracking::Track does.
+handed to TrackReferenceKeyFrame, as Tracking::Track does (src/Tracking.cc:2880-2890), which runs on the
+device too (orb_track_reference_kf_device: SearchByBoW with ORBmatcher(0.7, true) against the reference
+keyframe -> PoseOptimization from the last frame's pose -> the outlier discard):
+
+    res = chain.track(cur, last, local, pose7_pred).sync()
+    if res["status"] & (ORB_TRACK_FAIL_SEARCH | ORB_TRACK_FAIL_MAP):
+        bow = voc.transform_frames_device(desc, counts)                  # Frame::ComputeBoW
+        cur_bow = DeviceKeyFrame((kps, desc, counts), bow, f, ...)       # the frame as SearchByBoW reads it
+        ref = TrackReferenceKeyFrame(cap).track(ref_kf, point_ok, observed, xyz, cur_bow, cur, pose7_last).sync()
+        tracked = ref["status"] == 0     # else ORB_TRACK_REF_FAIL_BOW (< 15 matches) / ORB_TRACK_REF_FAIL_MAP
 
 The current frame is frame `f` of device arrays (ORBextractor.extract_batch_device, optionally
 undistort_keypoints_device, compute_stereo_matches_batch_device).  The last frame's tracked map points
@@ -28,7 +37,8 @@ are a table indexed by its keypoints (Frame::mvpMapPoints with MapPoint::GetWorl
 Observations); the local map (Tracking::mvpLocalMapPoints, as UpdateLocalMap leaves it) is a second
 table with the fields isInFrustum reads.  What the chain does not cover (the caller's): the motion
 model's pose prediction (mVelocity * mLastFrame.GetPose()), UpdateLocalMap's keyframe / point
-selection, the MapPoint counters (IncreaseVisible / IncreaseFound) and the IMU / relocalisation paths.
+selection, the MapPoint counters (IncreaseVisible / IncreaseFound), the IMU paths and relocalisation's
+PnP / RANSAC (its per-candidate SearchByBoW is ORBmatcher.SearchByBoWDevice).
 """
 from __future__ import annotations
 
@@ -76,6 +86,12 @@ class TrackingChainBuffers(ctypes.Structure):  # orb_tracking_chain_buffers_t
                                                "taken", "scratch", "status")]
 
 ORB_TRACK_RETRIED, ORB_TRACK_FAIL_SEARCH, ORB_TRACK_FAIL_MAP = 1, 2, 4
+ORB_TRACK_REF_FAIL_BOW, ORB_TRACK_REF_FAIL_MAP = 8, 16
+
+
+class TrackReferenceKFBuffers(ctypes.Structure):  # orb_track_reference_kf_buffers_t
+    _fields_ = [(k, ctypes.c_void_p) for k in ("match", "n_match", "frame", "edges", "edge_kp", "outlier", "pose",
+                                               "inliers", "n_out", "scratch", "status")]
 
 
 def _alloc_scratch(need: int, have, device):
@@ -333,6 +349,79 @@ class TrackingChain:
                                             ctypes.c_void_p(st.cuda_stream)),
               "orb_tracking_chain_device")
         return TrackResult(self, st)
+
+
+class ReferenceTrackResult:
+    """Device outputs of one TrackReferenceKeyFrame.track call (valid once the stream reaches them)."""
+
+    def __init__(self, owner, stream):
+        self.owner, self.stream = owner, stream
+
+    def sync(self) -> dict:
+        """Wait for the stream and return host copies: n_match (SearchByBoW's return), match (per keypoint
+        the reference keyframe's feature whose map point it holds, after the discard), pose (SE3Quat
+        vector), frame / edges / edge_kp / outlier (the PoseOptimization graph), inliers, n_kept (nmatches
+        after the discard), n_map (nmatchesMap), status (0 or an ORB_TRACK_REF_* bit)."""
+        o = self.owner
+        self.stream.synchronize()
+        fr = o.frame.cpu().numpy().view(POSE_FRAME_DTYPE).reshape(1)
+        ne = int(fr[0]["n_edges"])
+        return dict(frame=fr, n_match=int(o.n_match[0]), match=o.match.cpu().numpy(), pose=o.pose.cpu().numpy(),
+                    edges=o.edges[:ne].cpu().numpy().view(POSE_EDGE_DTYPE).reshape(-1),
+                    edge_kp=o.edge_kp[:ne].cpu().numpy(), outlier=o.outlier[:ne].cpu().numpy().astype(bool),
+                    inliers=int(o.inliers[0]), n_kept=int(o.n_out[0]), n_map=int(o.n_out[1]), status=int(o.status[0]))
+
+
+class TrackReferenceKeyFrame:
+    """Tracking::TrackReferenceKeyFrame (src/Tracking.cc:3931-4000) on the device for frames of up to `cap`
+    keypoints (orb_track_reference_kf_device): SearchByBoW(mpReferenceKF, mCurrentFrame) with
+    ORBmatcher(0.7, true), fewer than 15 matches -> ORB_TRACK_REF_FAIL_BOW; PoseOptimization from the last
+    frame's pose; the outlier discard; nmatchesMap < 10 -> ORB_TRACK_REF_FAIL_MAP unless `imu` (the IMU
+    sensors return true).  No host round trip between the stages."""
+
+    def __init__(self, cap: int, device=None, imu: bool = False):
+        import torch
+        self.device = torch.device(device if device is not None else "cuda")
+        self.cap, self.imu = int(cap), bool(imu)
+        self.matcher = ORBmatcher(0.7, True)
+        d, c = self.device, self.cap
+        self.match = torch.empty(c, dtype=torch.int32, device=d)
+        self.n_match = torch.zeros(1, dtype=torch.int32, device=d)
+        self.frame = torch.zeros(POSE_FRAME_DTYPE.itemsize, dtype=torch.uint8, device=d)
+        self.edges = torch.empty((c, POSE_EDGE_DTYPE.itemsize), dtype=torch.uint8, device=d)
+        self.edge_kp = torch.empty(c, dtype=torch.int32, device=d)
+        self.outlier = torch.empty(c, dtype=torch.uint8, device=d)
+        self.pose = torch.zeros(7, dtype=torch.float64, device=d)
+        self.inliers = torch.zeros(1, dtype=torch.int32, device=d)
+        self.n_out = torch.zeros(2, dtype=torch.int32, device=d)
+        self.status = torch.zeros(1, dtype=torch.int32, device=d)
+        need = int(_lib.load().orb_track_reference_kf_scratch_bytes(c))
+        self._scratch = torch.empty(need, dtype=torch.uint8, device=d)
+        self._h = self.matcher._handle()
+        self._bufs = TrackReferenceKFBuffers(
+            self.match.data_ptr(), self.n_match.data_ptr(), self.frame.data_ptr(), self.edges.data_ptr(),
+            self.edge_kp.data_ptr(), self.outlier.data_ptr(), self.pose.data_ptr(), self.inliers.data_ptr(),
+            self.n_out.data_ptr(), self._scratch.data_ptr(), self.status.data_ptr())
+
+    def track(self, ref_kf, point_ok, observed, xyz, cur_bow, cur: DeviceFrame, pose7, stream=None) -> ReferenceTrackResult:
+        """Enqueue the fallback for `cur` on `stream`.  ref_kf: the reference keyframe (a DeviceKeyFrame);
+        point_ok / observed / xyz: per keyframe feature, CUDA tensors of its capacity -- the map point is
+        non-NULL and not isBad() (uint8), has Observations() > 0 (uint8, None: all) and its GetWorldPos()
+        (float32 [cap, 3]).  cur_bow: `cur` as SearchByBoW reads it (a DeviceKeyFrame over the same
+        features with the BoW transform's FeatureVector).  pose7: mLastFrame.GetPose() as the SE3Quat
+        vector PoseOptimization starts from."""
+        import torch
+        if cur.cap != self.cap or cur_bow.cap != self.cap:
+            raise ValueError(f"frame capacity {cur.cap} / {cur_bow.cap} differs from the buffers' {self.cap}")
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        p0 = np.ascontiguousarray(pose7, np.float64).reshape(7)
+        self._keep = (ref_kf, point_ok, observed, xyz, cur_bow, cur)
+        check(_lib.load().orb_track_reference_kf_device(
+            self._h, ctypes.byref(ref_kf.view()), None if point_ok is None else point_ok.data_ptr(),
+            None if observed is None else observed.data_ptr(), xyz.data_ptr(), ctypes.byref(cur_bow.view()),
+            ctypes.byref(cur.view()), cur.mvInvLevelSigma2.ctypes.data, p0.ctypes.data, int(self.imu),
+            ctypes.byref(self._bufs), ctypes.c_void_p(st.cuda_stream)), "orb_track_reference_kf_device")
+        return ReferenceTrackResult(self, st)
 
 
 class TrackingChainFrame(ctypes.Structure):  # orb_tracking_chain_frame_t
