@@ -456,6 +456,73 @@ int orb_is_in_frustum_pose_device(const orb_frustum_frame_t* frame, const double
                                   float viewing_cos_limit, uint8_t* d_in_view, float* d_proj, float* d_depth,
                                   int32_t* d_level, float* d_view_cos, void* stream);
 
+/* ---- ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th, bRight = false) (src/ORBmatcher.cc:1326-1534)
+ * The search half (steps 1-6, :1356-1506) of the matcher LocalMapping::SearchInNeighbors runs once per
+ * target keyframe and once in the other direction (src/LocalMapping.cc:917-1066), for jobs (keyframe k,
+ * point i), k < n_kfs, i < points->n: all keyframes share one point set.  Single camera (NLeft == -1).  Per
+ * job: Pc = Rcw P + tcw; Pc.z < 0 rejected; (u, v) = Pinhole::project; KeyFrame::IsInImage (half open: u >=
+ * min_x && u < max_x, v likewise); ur = u - bf / Pc.z; the distance to Ow inside [0.8 mfMinDistance, 1.2
+ * mfMaxDistance]; PO . normal >= 0.5 dist; MapPoint::PredictScale(dist, pKF) (src/MapPoint.cc:688-706);
+ * radius = th * mvScaleFactors[level]; KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:843-891: cells ix outer,
+ * iy inner, a cell's keypoints in index order, |dx| < r && |dy| < r, no level filter); per keypoint the
+ * octave in [level - 1, level] and the chi-square gate (mvuRight[idx] >= 0: (ex^2 + ey^2 + er^2) *
+ * mvInvLevelSigma2[octave] > 7.8 rejected, else (ex^2 + ey^2) * ... > 5.99; the float product compared in
+ * double); the first minimum of DescriptorDistance from 256 / -1.  Float arithmetic as the reference build
+ * contracts it (oracle/orb_frustum_oracle.cpp, oracle/orb_projection_oracle.cpp).
+ *   best_idx[k * n + i] = bestIdx when bestDist <= TH_LOW (50), else -1 (also for a skipped job);
+ *   best_dist[k * n + i] = bestDist, the minimum found (256 when none or skipped).
+ * The map mutation (step 7, :1506-1527: Replace / AddObservation / AddMapPoint) stays with the caller
+ * (include/orbgpu_matcher.hpp), like every other map write.  The keyframe's grid (KeyFrame::mGrid) is
+ * built on the device from kps_un and the bounds. */
+typedef struct orb_fuse_kf {
+    orb_frame_view_t frame;         /* N, mvKeysUn, mDescriptors, mvuRight, bounds, grid inverses, camera, mbf,
+                                       levels, mvScaleFactors, GetPose() (`b` is not read); nlevels <= 12 */
+    float Ow[3];                    /* GetCameraCenter() */
+    const float* inv_level_sigma2;  /* mvInvLevelSigma2 (nlevels) */
+    float log_scale_factor;         /* mfLogScaleFactor */
+} orb_fuse_kf_t;
+
+/* The same around a device-resident keyframe: the count is read on the device (cap <= 16384); a negative
+ * or over-cap count (a frame its producer flagged ORB_ERR_CAPACITY) gives no matches for that keyframe
+ * (-1 / 256 everywhere).  scale_factors and inv_level_sigma2 are host arrays. */
+typedef struct orb_fuse_kf_device {
+    orb_frame_device_t frame;
+    float Ow[3];
+    const float* inv_level_sigma2;  /* host: mvInvLevelSigma2 (nlevels) */
+    float log_scale_factor;
+} orb_fuse_kf_device_t;
+
+/* vpMapPoints as flat arrays (host memory); n <= 2^20. */
+typedef struct orb_fuse_points {
+    int32_t n;
+    const float* pos;               /* GetWorldPos(), n x 3 */
+    const float* normal;            /* GetNormal(), n x 3 */
+    const float* min_dist;          /* mfMinDistance (raw, as orb_is_in_frustum takes it) */
+    const float* max_dist;          /* mfMaxDistance */
+    const uint8_t* desc;            /* GetDescriptor(), n x 32 */
+} orb_fuse_points_t;
+
+/* The same on device arrays (desc 16-byte aligned); n on the host. */
+typedef struct orb_fuse_points_device {
+    int32_t n;
+    const float* pos;
+    const float* normal;
+    const float* min_dist;
+    const float* max_dist;
+    const uint8_t* desc;
+} orb_fuse_points_device_t;
+
+/* Host memory, synchronous, through the handle's staging buffers and stream.  skip[k * n + i] != 0: the
+ * job is not searched (vpMapPoints[i] NULL, isBad() or IsInKeyFrame(kfs[k])); skip may be NULL (no job
+ * skipped), best_dist may be NULL.  th > 0.  n == 0 or n_kfs == 0: ORB_OK, nothing launched. */
+int orb_fuse(orb_matcher_t m, const orb_fuse_kf_t* kfs, int n_kfs, const orb_fuse_points_t* points,
+             const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist);
+/* The same on device arrays (d_skip, d_best_idx, d_best_dist: n_kfs x n), asynchronous on `stream`;
+ * scratch (the grids) is allocated and freed on `stream`.  n_kfs <= 65535. */
+int orb_fuse_device(orb_matcher_t m, const orb_fuse_kf_device_t* kfs, int n_kfs,
+                    const orb_fuse_points_device_t* points, const uint8_t* d_skip, float th, int32_t* d_best_idx,
+                    int32_t* d_best_dist, void* stream);
+
 /* ---- Frame::ComputeStereoMatches (src/Frame.cc:1102-1358) ------------------------------------ */
 
 /* Stereo matching of a rectified pair, on the two extractors' device pyramids (mvImagePyramid of

@@ -9,6 +9,9 @@
  *   int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)   (:1951-2185)
  *   int SearchByProjection(Frame& F, const vector<MapPoint*>&, th, bFarPoints, thFarPoints) (:46-240)
  *   int SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)   (:260-494)
+ *   int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th = 3.0)          (:1326-1534, bRight = false)
+ *   void Fuse(const vector<KeyFrame*>&, const vector<MapPoint*>&, th, vector<int>& vnFused)   (the forward loop
+ *                                                             of SearchInNeighbors, src/LocalMapping.cc:991-1001)
  *
  * The class translates the reference's KeyFrame / Frame / MapPoint objects into the ABI's flat views
  * (orb_kf_view_t, orb_frame_view_t, orb_last_points_t, orb_local_points_t), calls the HIP matcher,
@@ -42,6 +45,14 @@
  *     static int Observations(MapPoint*);  static bool IsBad(MapPoint*);
  *     static void WorldPos(MapPoint*, float X[3]);  static void Descriptor(MapPoint*, uint8_t d[32]);
  *     static void Track(MapPoint*, orbgpu::TrackFields*);   // mbTrackInView, mTrackProjX/Y/XR, ...
+ *     // Fuse only (int Fuse(KeyFrame*, const vector<MapPoint*>&, th) :1326-1534 and its batched overload)
+ *     static void FuseGeometry(KeyFrame*, orb_fuse_kf_t*);  // frame.min_x .. max_y, grid_inv_w / h, bf, Tcw =
+ *                                   // GetPose(); Ow = GetCameraCenter(); mvInvLevelSigma2; mfLogScaleFactor
+ *     static MapPoint* GetMapPoint(KeyFrame*, int idx);   static void AddMapPoint(KeyFrame*, MapPoint*, int idx);
+ *     static bool IsInKeyFrame(MapPoint*, KeyFrame*);     static void AddObservation(MapPoint*, KeyFrame*, int idx);
+ *     static void Replace(MapPoint* pMP, MapPoint* by);   // pMP->Replace(by)
+ *     static void Normal(MapPoint*, float n[3]);          // GetNormal()
+ *     static float MinDistance(MapPoint*);  static float MaxDistance(MapPoint*);   // mfMinDistance, mfMaxDistance
  *   };
  *
  * Scope: pinhole single-camera frames and keyframes (the configuration the ABI covers).  For the
@@ -57,6 +68,7 @@
 #define ORBGPU_MATCHER_HPP
 
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -159,6 +171,62 @@ struct KfViewStore {
     }
     KfViewStore(const KfViewStore&) = delete;
     KfViewStore& operator=(const KfViewStore&) = delete;
+};
+
+// A keyframe's orb_fuse_kf_t (it points into the keyframe's own arrays).
+template <class A>
+struct FuseKfStore {
+    orb_fuse_kf_t view{};
+    explicit FuseKfStore(typename A::KeyFrame* k) {
+        float K[4];
+        A::Pinhole(k, K);
+        orb_frame_view_t& f = view.frame;
+        f.n = A::N(k);
+        f.kps_un = A::KeysUn(k);
+        f.desc = A::Descriptors(k);
+        f.u_right = A::URight(k);
+        f.fx = K[0];
+        f.fy = K[1];
+        f.cx = K[2];
+        f.cy = K[3];
+        f.nlevels = A::Levels(k);
+        f.scale_factors = A::ScaleFactors(k);
+        A::FuseGeometry(k, &view);  // bounds, grid inverses, mbf, GetPose(), Ow, mvInvLevelSigma2, mfLogScaleFactor
+    }
+};
+
+// vpMapPoints as orb_fuse_points_t: dead[i] = NULL or isBad() (zero rows, skipped for every keyframe).
+template <class A>
+struct FusePointStore {
+    orb_fuse_points_t view{};
+    std::vector<uint8_t> dead, desc;
+    std::vector<float> pos, normal, min_dist, max_dist;
+    explicit FusePointStore(const std::vector<typename A::MapPoint*>& pts) {
+        const size_t n = pts.size();
+        dead.assign(n, 0);
+        desc.assign(32 * n, 0);
+        pos.assign(3 * n, 0.f);
+        normal.assign(3 * n, 0.f);
+        min_dist.assign(n, 0.f);
+        max_dist.assign(n, 0.f);
+        for (size_t i = 0; i < n; ++i) {
+            if (!pts[i] || A::IsBad(pts[i])) {
+                dead[i] = 1;
+                continue;
+            }
+            A::WorldPos(pts[i], &pos[3 * i]);
+            A::Normal(pts[i], &normal[3 * i]);
+            min_dist[i] = A::MinDistance(pts[i]);
+            max_dist[i] = A::MaxDistance(pts[i]);
+            A::Descriptor(pts[i], &desc[32 * i]);
+        }
+        view.n = (int32_t)n;
+        view.pos = pos.data();
+        view.normal = normal.data();
+        view.min_dist = min_dist.data();
+        view.max_dist = max_dist.data();
+        view.desc = desc.data();
+    }
 };
 }  // namespace detail
 
@@ -358,6 +426,85 @@ public:
         return n;
     }
 
+    // src/ORBmatcher.cc:1326-1534 without bRight (two-camera rigs keep the CPU body: Supports(pKF) is false
+    // for NLeft != -1).  One orb_fuse call for the search (steps 1-6), then step 7 (:1506-1527) here, in
+    // index order, with the skip tests evaluated again at apply time.
+    static bool Supports(KeyFrame* k) { return A::SingleCamera(k); }
+    int Fuse(KeyFrame* pKF, const std::vector<MapPoint*>& vpMapPoints, const float th = 3.0f) {
+        std::vector<int> n;
+        Fuse(std::vector<KeyFrame*>{pKF}, vpMapPoints, th, n);
+        return n[0];
+    }
+
+    // The forward loop of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:991-1001) in one launch:
+    // vnFused[k] = what Fuse(vpKFs[k], vpMapPoints, th) returns when the calls are made one after another,
+    // and the map ends in the same state.  Inside one call a point's search does not depend on what earlier
+    // points did to the map; across calls it does in one way: pMPinKF->Replace(pMP) ends in
+    // pMP->ComputeDistinctiveDescriptors() (src/MapPoint.cc:377), so a survivor may search the later
+    // keyframes with another descriptor.  Before a keyframe is applied, every live point whose descriptor
+    // is no longer the one sent is searched again against that keyframe (one small orb_fuse call per
+    // keyframe at most).  Failures: the first call failing mutates nothing and every count is 0; a failing
+    // re-search stops there (the keyframes already applied stay applied, the rest count 0).
+    void Fuse(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMapPoints, const float th,
+              std::vector<int>& vnFused) {
+        const size_t K = vpKFs.size(), n = vpMapPoints.size();
+        vnFused.assign(K, 0);
+        if (K == 0 || n == 0) return;
+        std::vector<detail::FuseKfStore<A>> kfs;
+        kfs.reserve(K);
+        for (KeyFrame* k : vpKFs) kfs.emplace_back(k);
+        std::vector<orb_fuse_kf_t> views(K);
+        for (size_t k = 0; k < K; ++k) views[k] = kfs[k].view;
+        detail::FusePointStore<A> sent(vpMapPoints);
+        std::vector<uint8_t> skip(K * n);
+        for (size_t k = 0; k < K; ++k)
+            for (size_t i = 0; i < n; ++i) skip[k * n + i] = sent.dead[i] || A::IsInKeyFrame(vpMapPoints[i], vpKFs[k]);
+        std::vector<int32_t> best(K * n, -1);
+        if (Failed(orb_fuse(Handle(), views.data(), (int)K, &sent.view, skip.data(), th, best.data(), nullptr), "orb_fuse"))
+            return;
+        for (size_t k = 0; k < K; ++k) {
+            KeyFrame* pKF = vpKFs[k];
+            // the points whose descriptor changed since it was sent: their results for this keyframe are stale
+            std::vector<MapPoint*> again;
+            std::vector<size_t> again_i;
+            for (size_t i = 0; k > 0 && i < n; ++i) {
+                MapPoint* pMP = vpMapPoints[i];
+                if (sent.dead[i] || A::IsBad(pMP) || A::IsInKeyFrame(pMP, pKF)) continue;
+                uint8_t d[32];
+                A::Descriptor(pMP, d);
+                if (std::memcmp(d, &sent.desc[32 * i], 32) == 0) continue;
+                again.push_back(pMP);
+                again_i.push_back(i);
+            }
+            if (!again.empty()) {
+                detail::FusePointStore<A> now(again);
+                std::vector<int32_t> b(again.size(), -1);
+                if (Failed(orb_fuse(Handle(), &views[k], 1, &now.view, nullptr, th, b.data(), nullptr), "orb_fuse"))
+                    return;
+                for (size_t j = 0; j < again.size(); ++j) best[k * n + again_i[j]] = b[j];
+            }
+            int nFused = 0;
+            for (size_t i = 0; i < n; ++i) {  // step 7 (:1506-1527)
+                MapPoint* pMP = vpMapPoints[i];
+                if (!pMP || A::IsBad(pMP) || A::IsInKeyFrame(pMP, pKF)) continue;  // (:1361-1376, at apply time)
+                const int32_t bestIdx = best[k * n + i];
+                if (bestIdx < 0) continue;
+                MapPoint* pMPinKF = A::GetMapPoint(pKF, bestIdx);
+                if (pMPinKF) {
+                    if (!A::IsBad(pMPinKF)) {
+                        if (A::Observations(pMPinKF) > A::Observations(pMP)) A::Replace(pMP, pMPinKF);
+                        else A::Replace(pMPinKF, pMP);
+                    }
+                } else {
+                    A::AddObservation(pMP, pKF, bestIdx);
+                    A::AddMapPoint(pKF, pMP, bestIdx);
+                }
+                ++nFused;
+            }
+            vnFused[k] = nFused;
+        }
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -491,6 +638,39 @@ struct ORBSLAM3MatcherAccess {
     static void SetDescriptor(MapPoint* p, const uint8_t d[32]) {
         std::unique_lock<std::mutex> lock(p->mMutexFeatures);
         p->mDescriptor = cv::Mat(1, 32, CV_8U, const_cast<uint8_t*>(d)).clone();
+    }
+    // Fuse (KeyFrame's bounds and grid inverses are public members; MapPoint's raw distances are
+    // protected: the integration's friend declaration covers them, as for SetDescriptor)
+    static void FuseGeometry(KeyFrame* k, orb_fuse_kf_t* v) {
+        orb_frame_view_t& f = v->frame;
+        f.min_x = k->mnMinX; f.max_x = k->mnMaxX; f.min_y = k->mnMinY; f.max_y = k->mnMaxY;
+        f.grid_inv_w = k->mfGridElementWidthInv;
+        f.grid_inv_h = k->mfGridElementHeightInv;
+        f.bf = k->mbf; f.b = k->mb;
+        const Eigen::Matrix<float, 3, 4> T = k->GetPose().matrix3x4();
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) f.Tcw[4 * r + c] = T(r, c);
+        const Eigen::Vector3f Ow = k->GetCameraCenter();
+        for (int r = 0; r < 3; ++r) v->Ow[r] = Ow(r);
+        v->inv_level_sigma2 = k->mvInvLevelSigma2.data();
+        v->log_scale_factor = k->mfLogScaleFactor;
+    }
+    static MapPoint* GetMapPoint(KeyFrame* k, int idx) { return k->GetMapPoint(idx); }
+    static void AddMapPoint(KeyFrame* k, MapPoint* p, int idx) { k->AddMapPoint(p, idx); }
+    static bool IsInKeyFrame(MapPoint* p, KeyFrame* k) { return p->IsInKeyFrame(k); }
+    static void AddObservation(MapPoint* p, KeyFrame* k, int idx) { p->AddObservation(k, idx); }
+    static void Replace(MapPoint* p, MapPoint* by) { p->Replace(by); }
+    static void Normal(MapPoint* p, float n[3]) {
+        const Eigen::Vector3f v = p->GetNormal();
+        n[0] = v(0); n[1] = v(1); n[2] = v(2);
+    }
+    static float MinDistance(MapPoint* p) {
+        std::unique_lock<std::mutex> lock(p->mMutexPos);
+        return p->mfMinDistance;
+    }
+    static float MaxDistance(MapPoint* p) {
+        std::unique_lock<std::mutex> lock(p->mMutexPos);
+        return p->mfMaxDistance;
     }
     static void Track(MapPoint* p, TrackFields* t) {
         t->in_view = p->mbTrackInView;

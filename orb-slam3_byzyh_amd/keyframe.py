@@ -129,7 +129,7 @@ class Frame:
     """The Frame fields SearchByProjection reads (src/Frame.cc; pinhole, no second camera)."""
 
     def __init__(self, keys_un, descriptors, Tcw, camera, scale_factors, width, height, bf=0.0, u_right=None,
-                 map_points=None):
+                 map_points=None, Ow=None, inv_level_sigma2=None, log_scale_factor=None):
         self.mvKeysUn = np.ascontiguousarray(keys_un, dtype=KEYPOINT_DTYPE)
         self.N = len(self.mvKeysUn)
         self.mDescriptors = np.ascontiguousarray(descriptors, dtype=np.uint8).reshape(self.N, 32)
@@ -145,6 +145,29 @@ class Frame:
         self.mfGridElementHeightInv = float(np.float32(FRAME_GRID_ROWS) / np.float32(self.mnMaxY - self.mnMinY))
         # tracked map points, for use as a LastFrame: dict with valid, observed, xyz, desc arrays
         self.map_points = map_points
+        # the KeyFrame fields ORBmatcher::Fuse reads besides the above (fuse_view): GetCameraCenter(),
+        # mvInvLevelSigma2, mfLogScaleFactor; None: derived from the pose / scale factors when first asked for
+        self.Ow = None if Ow is None else np.ascontiguousarray(Ow, dtype=np.float32).reshape(3)
+        self.mvInvLevelSigma2 = (None if inv_level_sigma2 is None
+                                 else np.ascontiguousarray(inv_level_sigma2, dtype=np.float32))
+        self.mfLogScaleFactor = None if log_scale_factor is None else float(np.float32(log_scale_factor))
+
+    def fuse_view(self) -> "FuseKfView":
+        """orb_fuse_kf_t of this frame used as a KeyFrame (ORBmatcher.Fuse).  Defaults for fields not given:
+        Ow = -Rcw^T tcw in float32, mvInvLevelSigma2 = 1 / mvScaleFactors^2 (src/Frame.cc:115-124),
+        mfLogScaleFactor = logf(mvScaleFactors[1])."""
+        if self.Ow is None:
+            R, t = self.Tcw[:, :3], self.Tcw[:, 3]
+            self.Ow = np.ascontiguousarray(-(R.T @ t), dtype=np.float32)
+        if self.mvInvLevelSigma2 is None:
+            s = self.mvScaleFactors
+            self.mvInvLevelSigma2 = np.ascontiguousarray(np.float32(1.0) / (s * s), dtype=np.float32)
+        if self.mfLogScaleFactor is None:
+            self.mfLogScaleFactor = float(logf(self.mvScaleFactors[1])) if len(self.mvScaleFactors) > 1 else 0.0
+        v = FuseKfView(self.view(), (ctypes.c_float * 3)(*[float(x) for x in self.Ow]), _ptr(self.mvInvLevelSigma2),
+                       self.mfLogScaleFactor)
+        self._keep_fuse = v
+        return v
 
     def view(self) -> FrameView:
         v = FrameView(self.N, _ptr(self.mvKeysUn), _ptr(self.mDescriptors), _ptr(self.mvuRight), self.mnMinX,
@@ -165,6 +188,34 @@ class Frame:
         v.Tcw[:] = [float(x) for x in self.Tcw.reshape(-1)]
         self._keep_last = v
         return v
+
+
+class FuseKfView(ctypes.Structure):  # orb_fuse_kf_t
+    _fields_ = [("frame", FrameView), ("Ow", ctypes.c_float * 3), ("inv_level_sigma2", ctypes.c_void_p),
+                ("log_scale_factor", ctypes.c_float)]
+
+
+class FusePointsView(ctypes.Structure):  # orb_fuse_points_t / orb_fuse_points_device_t
+    _fields_ = [("n", ctypes.c_int32), ("pos", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("min_dist", ctypes.c_void_p), ("max_dist", ctypes.c_void_p), ("desc", ctypes.c_void_p)]
+
+
+class FusePoints:
+    """vpMapPoints of ORBmatcher::Fuse as flat arrays: GetWorldPos, GetNormal (n x 3), the raw mfMinDistance /
+    mfMaxDistance and GetDescriptor (n x 32)."""
+
+    def __init__(self, pos, normal, min_dist, max_dist, desc):
+        self.pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+        self.n = len(self.pos)
+        self.normal = np.ascontiguousarray(normal, dtype=np.float32).reshape(self.n, 3)
+        self.min_dist = np.ascontiguousarray(min_dist, dtype=np.float32).reshape(self.n)
+        self.max_dist = np.ascontiguousarray(max_dist, dtype=np.float32).reshape(self.n)
+        self.desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(self.n, 32)
+
+    def view(self) -> FusePointsView:
+        self._v = FusePointsView(self.n, _ptr(self.pos), _ptr(self.normal), _ptr(self.min_dist), _ptr(self.max_dist),
+                                 _ptr(self.desc))
+        return self._v
 
 
 class LocalPointsView(ctypes.Structure):

@@ -7,7 +7,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .keyframe import DeviceKeyFrame, Frame, KeyFrame, KfDeviceView, KfView, LocalMapPoints, PairGeom
+from .keyframe import (DeviceKeyFrame, Frame, FuseKfView, FusePoints, FusePointsView, KeyFrame, KfDeviceView, KfView,
+                       LocalMapPoints, PairGeom)
 
 TH_HIGH = 100  # src/ORBmatcher.cc:36
 TH_LOW = 50    # src/ORBmatcher.cc:37
@@ -170,6 +171,62 @@ class ORBmatcher:
                                                    out[1].data_ptr(), ctypes.c_void_p(st.cuda_stream)),
               "orb_search_by_bow_device")
         return out
+
+    def Fuse(self, kfs, points: FusePoints, th: float = 3.0, skip=None):
+        """The search half of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:
+        1356-1506) for every keyframe of `kfs` (a Frame carrying Ow / mvInvLevelSigma2 / mfLogScaleFactor, or a
+        list of them) against one point set in one launch: LocalMapping::SearchInNeighbors' forward loop, or
+        with one keyframe its reverse call.  skip[k, i] != 0: vpMapPoints[i] is NULL, isBad() or
+        IsInKeyFrame(kfs[k]).  Returns (best_idx [K, n], best_dist [K, n]) int32: bestIdx where bestDist <=
+        TH_LOW (else -1) and the minimum distance found (256: none).  Step 7, the map mutation, is the caller's."""
+        kfs = [kfs] if isinstance(kfs, Frame) else list(kfs)
+        K, n = len(kfs), points.n
+        idx = np.full((K, n), -1, np.int32)
+        dist = np.full((K, n), 256, np.int32)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.uint8)
+            if sk.size != K * n:
+                raise ValueError("skip: one flag per (keyframe, point)")
+        views = (FuseKfView * max(K, 1))(*[k.fuse_view() for k in kfs])
+        check(_lib.load().orb_fuse(self._handle(), views, K, ctypes.byref(points.view()),
+                                   None if sk is None else sk.ctypes.data, float(th), idx.ctypes.data, dist.ctypes.data),
+              "orb_fuse")
+        return idx, dist
+
+    def FuseDevice(self, kfs, points, th: float = 3.0, skip=None, Ow=None, log_scale_factor=None, stream=None,
+                   out=None):
+        """The same on device-resident keyframes and points (orb_fuse_device), asynchronous on `stream`.  kfs:
+        tracking.DeviceFrame objects (their counts are read on the device; a flagged count gives -1 / 256 for
+        that keyframe); points: CUDA tensors (pos [n, 3], normal [n, 3], min_dist [n], max_dist [n] float32,
+        desc [n, 32] uint8); skip: uint8 [K, n] CUDA tensor or None; Ow: [K, 3] camera centres (None: -Rcw^T tcw
+        in float32); log_scale_factor: mfLogScaleFactor (None: logf(mvScaleFactors[1])).  Returns (best_idx,
+        best_dist) int32 [K, n] CUDA tensors."""
+        import torch
+        from .keyframe import logf
+        from .tracking import FrameDeviceView, FuseKfDeviceView  # (tracking imports this module)
+
+        kfs = list(kfs)
+        pos, normal, min_dist, max_dist, desc = (t.contiguous() for t in points)
+        K, n, dev = len(kfs), int(pos.shape[0]), pos.device
+        if out is None:
+            out = (torch.empty((max(K, 1), max(n, 1)), dtype=torch.int32, device=dev),
+                   torch.empty((max(K, 1), max(n, 1)), dtype=torch.int32, device=dev))
+        views = (FuseKfDeviceView * max(K, 1))()
+        for k, kf in enumerate(kfs):
+            ow = -(kf.Tcw[:, :3].T @ kf.Tcw[:, 3]) if Ow is None else np.asarray(Ow, np.float32)[k]
+            lsf = logf(kf.mvScaleFactors[1]) if log_scale_factor is None else log_scale_factor
+            ctypes.memmove(ctypes.byref(views[k].frame), ctypes.byref(kf.view()), ctypes.sizeof(FrameDeviceView))
+            views[k].Ow[:] = [float(np.float32(x)) for x in ow]
+            views[k].inv_level_sigma2 = kf.mvInvLevelSigma2.ctypes.data
+            views[k].log_scale_factor = float(np.float32(lsf))
+        pv = FusePointsView(n, pos.data_ptr(), normal.data_ptr(), min_dist.data_ptr(), max_dist.data_ptr(), desc.data_ptr())
+        sk = None if skip is None else skip.contiguous()
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        check(_lib.load().orb_fuse_device(self._handle(), views, K, ctypes.byref(pv), None if sk is None else sk.data_ptr(),
+                                          float(th), out[0].data_ptr(), out[1].data_ptr(),
+                                          ctypes.c_void_p(st.cuda_stream)), "orb_fuse_device")
+        return out[0][:K, :n], out[1][:K, :n]
 
     @staticmethod
     def DescriptorDistance(a, b) -> int:

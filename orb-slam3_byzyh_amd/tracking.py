@@ -62,6 +62,11 @@ class FrameDeviceView(ctypes.Structure):  # orb_frame_device_t
                 ("Tcw", ctypes.c_float * 12)]
 
 
+class FuseKfDeviceView(ctypes.Structure):  # orb_fuse_kf_device_t (ORBmatcher.FuseDevice)
+    _fields_ = [("frame", FrameDeviceView), ("Ow", ctypes.c_float * 3), ("inv_level_sigma2", ctypes.c_void_p),
+                ("log_scale_factor", ctypes.c_float)]
+
+
 class LastPointsDeviceView(ctypes.Structure):  # orb_last_points_device_t
     _fields_ = [("n", ctypes.c_void_p), ("cap", ctypes.c_int32), ("valid", ctypes.c_void_p),
                 ("observed", ctypes.c_void_p), ("xyz", ctypes.c_void_p), ("desc", ctypes.c_void_p),
