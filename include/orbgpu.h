@@ -523,6 +523,122 @@ int orb_fuse_device(orb_matcher_t m, const orb_fuse_kf_device_t* kfs, int n_kfs,
                     const orb_fuse_points_device_t* points, const uint8_t* d_skip, float th, int32_t* d_best_idx,
                     int32_t* d_best_dist, void* stream);
 
+/* ---- LocalMapping::CreateNewMapPoints, the triangulation half (src/LocalMapping.cc:626-910) ----------
+ * For every match (idx1, idx2 = matches12[p][idx1] >= 0) of keyframe 1 against neighbour p, in one call:
+ * the parallax test (:720-783), GeometricTools::Triangulate (src/GeometricTools.cc:63-90) or
+ * KeyFrame::UnprojectStereo (src/KeyFrame.cc:905-924), the two depth tests (:794-800), the two reprojection
+ * chi-square tests (:804-860: 5.991 sigma2 mono, 7.8 sigma2 stereo, u2_r with keyframe 1's mbf as :853 has
+ * it) and the distance / octave test (:866-884).  Then the rule of the neighbour loop: upstream gives idx1 a
+ * map point as soon as one neighbour succeeds and later neighbours no longer match that idx1, so the
+ * smallest p whose job is ORB_NP_OK keeps it and every later ORB_NP_OK at the same idx1 becomes
+ * ORB_NP_TAKEN.  The survivors are emitted as records in upstream's creation order (p ascending, then idx1
+ * ascending), each with MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:567-642) of its two observations
+ * (reference keyframe = keyframe 1, level = kp1.octave).  A caller that stops early at CheckNewKeyFrames()
+ * (:568) before neighbour k uses the records with p < k: they are a prefix and do not depend on later
+ * neighbours.  Single pinhole camera (NLeft == -1, mpCamera2 == NULL); the two-camera branch (:665-715) is
+ * not implemented.  The baseline / median-depth pre-tests (:575-601) stay with the caller, who leaves a
+ * skipped neighbour out; step 6's map mutation (:888-909) stays with the caller too
+ * (include/orbgpu_matcher.hpp, ORBmatcher::CreateNewMapPoints).
+ *
+ * Float32 as upstream computes it, contractions as the reference build makes them (the list heads
+ * csrc/orb_newpoints.hip); invz = 1.0 / z in double, rounded; the chi-square sums compared as doubles with
+ * the double products 5.991 * sigma2 / 7.8 * sigma2; cos(2 atan2(mb / 2, depth)) in double, rounded once
+ * (as (d^2 - a^2) / (d^2 + a^2), with the libm pair's values for an infinite a or d).
+ * The 4x4 null vector is a float one-sided Jacobi (csrc/orb_svd4.h): at least as accurate as LAPACK's float SVD, not
+ * bit-identical to Eigen's JacobiSVD.  Comparisons keep upstream's form, so non-finite values fall through
+ * the same gates. */
+#define ORB_NP_NO_MATCH 0      /* matches12 < 0, an index past a count, or a pair flagged ORB_ERR_CAPACITY */
+#define ORB_NP_LOW_PARALLAX 1  /* the final else (:780-783): no stereo and very low parallax */
+#define ORB_NP_TRI_W_ZERO 2    /* Triangulate false: x3Dh(3) == 0 */
+#define ORB_NP_STEREO_DEPTH 3  /* UnprojectStereo false: mvDepth <= 0 */
+#define ORB_NP_Z1 4            /* z1 <= 0 */
+#define ORB_NP_Z2 5            /* z2 <= 0 */
+#define ORB_NP_CHI2_1 6        /* reprojection error in keyframe 1 */
+#define ORB_NP_CHI2_2 7        /* reprojection error in the neighbour */
+#define ORB_NP_DIST_ZERO 8     /* dist1 == 0 || dist2 == 0 */
+#define ORB_NP_FAR 9           /* mbFarPoints && (dist1 >= mThFarPoints || dist2 >= mThFarPoints) */
+#define ORB_NP_SCALE 10        /* ratioDist against ratioOctave * ratioFactor */
+#define ORB_NP_OK 11           /* the job triangulated and this neighbour keeps idx1 */
+#define ORB_NP_TAKEN 12        /* the job triangulated, an earlier neighbour already gave idx1 its point */
+
+/* What triangulation reads of a keyframe besides the search's view (host values unless noted). */
+typedef struct orb_newpoints_kf_extra {
+    float Tcw[12];                  /* GetPose().matrix3x4(), row-major */
+    float Ow[3];                    /* GetCameraCenter(), as orb_fuse takes it */
+    float mb, mbf, invfx, invfy;
+    const float* depth;             /* mvDepth (host entry: n host floats; device entry: cap device floats);
+                                       NULL = monocular (read only where u_right >= 0) */
+    const orb_keypoint_t* kps_raw;  /* mvKeys, which UnprojectStereo reads; NULL = the view's mvKeysUn */
+} orb_newpoints_kf_extra_t;
+
+/* Host keyframe: of `view` the call reads n, kps_un, u_right, fx..cy, nlevels, scale_factors, level_sigma2. */
+typedef struct orb_newpoints_kf {
+    orb_kf_view_t view;
+    orb_newpoints_kf_extra_t extra;
+} orb_newpoints_kf_t;
+
+/* Device keyframe: of `view` the call reads kps, n, u_right, cap, fx..cy, nlevels and the two host arrays. */
+typedef struct orb_newpoints_kf_device {
+    orb_kf_device_t view;
+    orb_newpoints_kf_extra_t extra;
+} orb_newpoints_kf_device_t;
+
+typedef struct orb_newpoints_params {
+    int32_t inertial;      /* mbInertial: the mono parallax limit is 0.9996 instead of 0.9998 */
+    int32_t far_points;    /* mbFarPoints */
+    float th_far_points;   /* mThFarPoints */
+    float ratio_factor;    /* 1.5f * mfScaleFactor of keyframe 1 */
+} orb_newpoints_params_t;
+
+/* One new map point (48 bytes), in creation order. */
+typedef struct orb_newpoint {
+    int32_t p;             /* the neighbour: kf2s[p] */
+    int32_t idx1, idx2;    /* the two observations */
+    float x3d[3];          /* the world position */
+    int32_t from_stereo;   /* bPointStereo */
+    float normal[3];       /* mNormalVector */
+    float min_dist;        /* mfMinDistance */
+    float max_dist;        /* mfMaxDistance */
+} orb_newpoint_t;
+
+/* The outputs of both entries, with C the row stride of matches12 (host entry: max(kf1 n, 1); device entry:
+ * kf1's cap): status [P x C] int32 (ORB_NP_*), x3d [P x C x 3] float (the position wherever one was
+ * computed, i.e. status >= ORB_NP_Z1; else 0), from_stereo [P x C] uint8, taken_by [C] int32 (the
+ * neighbour that keeps idx1, or -1), records [C] (an idx1 yields at most one point), n_new [1] int32. */
+typedef struct orb_newpoints_out {
+    int32_t* status;
+    float* x3d;
+    uint8_t* from_stereo;
+    int32_t* taken_by;
+    orb_newpoint_t* records;
+    int32_t* n_new;
+} orb_newpoints_out_t;
+
+/* Host arrays through the matcher handle's staging buffers and stream, synchronous.  matches12 [n_pairs x
+ * max(kf1 n, 1)] and n_matches [n_pairs] as orb_search_for_triangulation wrote them (n_matches NULL: no pair
+ * is flagged; a negative n_matches[p] yields no points for pair p and its matches12 row is not read).  n_pairs <=
+ * 1024, n <= 2^20 per keyframe and n_pairs * ceil(n1 / 256) <= 65536 (the record offsets come from a scan every
+ * block repeats over that many counts); an octave outside [0, nlevels) or, in a pair that is not flagged, a
+ * match index >= the neighbour's n gives ORB_ERR_ARG.  n_pairs == 0:
+ * ORB_OK, n_new = 0, taken_by = -1. */
+int orb_create_new_map_points(orb_matcher_t m, const orb_newpoints_kf_t* kf1, const orb_newpoints_kf_t* kf2s,
+                              int n_pairs, const orb_newpoints_params_t* params, const int32_t* matches12,
+                              const int32_t* n_matches, const orb_newpoints_out_t* out);
+
+/* Device-resident, asynchronous on `stream`: the host never waits for the kernels or for the search before them,
+ * and nothing is copied back.  Like orb_fuse_device the call does wait (hipEventSynchronize) until the previous
+ * device-entry call on the same handle has copied its argument records out of the handle's pinned slot, that is
+ * behind whatever was queued before that copy on its stream.  n_pairs * ceil(cap / 256) <= 65536.  d_matches12 [n_pairs x kf1 cap] and
+ * d_n_matches [n_pairs] exactly as orb_search_for_triangulation_device (one first keyframe) wrote them,
+ * ORB_ERR_CAPACITY in d_n_matches[p] included (no points for that pair).  `out` holds device pointers.
+ * Counts are read on the device and clamped to cap; a keyframe with a flagged count, an index past a
+ * count or an octave outside [0, nlevels) gives ORB_NP_NO_MATCH for the job.  The argument records and
+ * the scan's scratch are allocated and freed on `stream`. */
+int orb_create_new_map_points_device(orb_matcher_t m, const orb_newpoints_kf_device_t* kf1,
+                                     const orb_newpoints_kf_device_t* kf2s, int n_pairs,
+                                     const orb_newpoints_params_t* params, const int32_t* d_matches12,
+                                     const int32_t* d_n_matches, const orb_newpoints_out_t* out, void* stream);
+
 /* ---- Frame::ComputeStereoMatches (src/Frame.cc:1102-1358) ------------------------------------ */
 
 /* Stereo matching of a rectified pair, on the two extractors' device pyramids (mvImagePyramid of

@@ -69,6 +69,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -229,6 +230,9 @@ struct FusePointStore {
     }
 };
 }  // namespace detail
+
+template <class A>
+void ComputeDistinctiveDescriptors(const std::vector<typename A::MapPoint*>& points);
 
 template <class A>
 class ORBmatcher {
@@ -505,6 +509,101 @@ public:
         }
     }
 
+    // The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:603-910) for the neighbours
+    // that passed the caller's baseline / median-depth pre-tests (:575-601): the batched
+    // orb_search_for_triangulation, then orb_create_new_map_points on its matches, then step 6 (:888-909)
+    // here, through the access policy, in the order of the records (upstream's creation order):
+    //   pass 1, per record: NewMapPoint(x3d, pKF1), AddObservation(pMP, pKF1, idx1), AddObservation(pMP, pKF2,
+    //           idx2), AddMapPoint(pKF1, pMP, idx1), AddMapPoint(pKF2, pMP, idx2) -- two records of one
+    //           neighbour may share idx2: the later AddMapPoint overwrites, as upstream's does;
+    //   one batched ComputeDistinctiveDescriptors for all new points (a point's result depends on its own
+    //           observations only, so the batch equals upstream's per-point calls);
+    //   pass 2, per record: SetNormalAndDepth(pMP, normal, min_dist, max_dist) -- UpdateNormalAndDepth's
+    //           result for the two observations, from the record -- then `added(pMP)`, the caller's
+    //           mpAtlas->AddMapPoint(pMP) and mlpRecentAddedMapPoints.push_back(pMP).
+    // Returns the new map points in creation order (`records`, when given, receives their records).  A
+    // failing entry mutates nothing and returns no points.  A caller that honours CheckNewKeyFrames() (:568)
+    // between neighbours passes the neighbours it is willing to finish.  Accessor members used besides
+    // those of SearchForTriangulation:
+    //   static void NewPointsGeometry(KeyFrame*, orb_newpoints_kf_extra_t*);  // pose, Ow, mb, mbf, invfx/y, mvDepth, mvKeys
+    //   static MapPoint* NewMapPoint(const float x3d[3], KeyFrame* pRefKF);   // new MapPoint(x3D, pKF, map)
+    //   static void SetNormalAndDepth(MapPoint*, const float normal[3], float min_dist, float max_dist);
+    struct NewPointsParams {
+        bool inertial = false;        // mbInertial
+        bool far_points = false;      // mbFarPoints
+        float th_far_points = 0.f;    // mThFarPoints
+        float ratio_factor = 1.8f;    // 1.5f * pKF1->mfScaleFactor
+        bool coarse = false;          // bCoarse of the search (:607)
+    };
+    std::vector<MapPoint*> CreateNewMapPoints(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2,
+                                              const NewPointsParams& prm,
+                                              const std::function<void(MapPoint*)>& added = nullptr,
+                                              std::vector<orb_newpoint_t>* records = nullptr) {
+        std::vector<MapPoint*> created;
+        if (records) records->clear();
+        const size_t p = vpKF2.size();
+        if (p == 0) return created;
+        detail::KfViewStore<A> v1(pKF1);
+        std::vector<std::unique_ptr<detail::KfViewStore<A>>> v2;
+        std::vector<orb_kf_view_t> views(p);
+        std::vector<orb_kf_pair_geom_t> geoms(p);
+        std::vector<orb_newpoints_kf_t> nk(p);
+        orb_newpoints_kf_t nk1{};
+        nk1.view = v1.view;
+        A::NewPointsGeometry(pKF1, &nk1.extra);
+        for (size_t i = 0; i < p; ++i) {
+            v2.emplace_back(new detail::KfViewStore<A>(vpKF2[i]));
+            views[i] = v2.back()->view;
+            geoms[i] = A::PairGeometry(pKF1, vpKF2[i]);
+            nk[i] = orb_newpoints_kf_t{};
+            nk[i].view = views[i];
+            A::NewPointsGeometry(vpKF2[i], &nk[i].extra);
+        }
+        const int n1 = v1.view.n;
+        const size_t C = n1 > 0 ? (size_t)n1 : 1;
+        std::vector<int32_t> m12(p * C, -1), cnt(p, 0);
+        if (Failed(orb_search_for_triangulation(Handle(), &v1.view, views.data(), geoms.data(), (int)p, 0,
+                                                prm.coarse ? 1 : 0, m12.data(), cnt.data()),
+                   "orb_search_for_triangulation"))
+            return created;
+        std::vector<int32_t> status(p * C), taken(C);
+        std::vector<float> x3d(3 * p * C);
+        std::vector<uint8_t> from_stereo(p * C);
+        std::vector<orb_newpoint_t> rec(C);
+        int32_t n_new = 0;
+        const orb_newpoints_params_t prms{prm.inertial ? 1 : 0, prm.far_points ? 1 : 0, prm.th_far_points, prm.ratio_factor};
+        const orb_newpoints_out_t out{status.data(), x3d.data(), from_stereo.data(), taken.data(), rec.data(), &n_new};
+        if (Failed(orb_create_new_map_points(Handle(), &nk1, nk.data(), (int)p, &prms, m12.data(), cnt.data(), &out),
+                   "orb_create_new_map_points"))
+            return created;
+        if (n_new < 0 || (size_t)n_new > C) return created;
+        for (int r = 0; r < n_new; ++r) {  // (a conforming library reports none of these: nothing is mutated)
+            const orb_newpoint_t& q = rec[r];
+            if (q.p < 0 || (size_t)q.p >= p || q.idx1 < 0 || q.idx1 >= n1 || q.idx2 < 0 || q.idx2 >= views[q.p].n) {
+                Failed(ORB_ERR_INTERNAL, "orb_create_new_map_points (record out of range)");
+                return created;
+            }
+        }
+        created.reserve(n_new);
+        for (int r = 0; r < n_new; ++r) {  // pass 1 (:888-898)
+            const orb_newpoint_t& q = rec[r];
+            KeyFrame* pKF2 = vpKF2[q.p];
+            MapPoint* pMP = A::NewMapPoint(q.x3d, pKF1);
+            A::AddObservation(pMP, pKF1, q.idx1);
+            A::AddObservation(pMP, pKF2, q.idx2);
+            A::AddMapPoint(pKF1, pMP, q.idx1);
+            A::AddMapPoint(pKF2, pMP, q.idx2);
+            created.push_back(pMP);
+        }
+        orbgpu::ComputeDistinctiveDescriptors<A>(created);  // (:901), one launch
+        for (int r = 0; r < n_new; ++r) {  // pass 2 (:904-909)
+            A::SetNormalAndDepth(created[r], rec[r].normal, rec[r].min_dist, rec[r].max_dist);
+            if (added) added(created[r]);
+        }
+        if (records) records->assign(rec.begin(), rec.begin() + n_new);
+        return created;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 
@@ -671,6 +770,26 @@ struct ORBSLAM3MatcherAccess {
     static float MaxDistance(MapPoint* p) {
         std::unique_lock<std::mutex> lock(p->mMutexPos);
         return p->mfMaxDistance;
+    }
+    // CreateNewMapPoints (mfMinDistance / mfMaxDistance through the friend declaration, as above)
+    static void NewPointsGeometry(KeyFrame* k, orb_newpoints_kf_extra_t* e) {
+        const Eigen::Matrix<float, 3, 4> T = k->GetPose().matrix3x4();
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) e->Tcw[4 * r + c] = T(r, c);
+        const Eigen::Vector3f Ow = k->GetCameraCenter();
+        for (int r = 0; r < 3; ++r) e->Ow[r] = Ow(r);
+        e->mb = k->mb; e->mbf = k->mbf; e->invfx = k->invfx; e->invfy = k->invfy;
+        e->depth = k->mvDepth.empty() ? nullptr : k->mvDepth.data();
+        e->kps_raw = k->mvKeys.empty() ? nullptr : reinterpret_cast<const orb_keypoint_t*>(k->mvKeys.data());
+    }
+    static MapPoint* NewMapPoint(const float x3d[3], KeyFrame* pRefKF) {
+        return new MapPoint(Eigen::Vector3f(x3d[0], x3d[1], x3d[2]), pRefKF, pRefKF->GetMap());
+    }
+    static void SetNormalAndDepth(MapPoint* p, const float n[3], float min_dist, float max_dist) {
+        std::unique_lock<std::mutex> lock(p->mMutexPos);
+        p->mfMaxDistance = max_dist;
+        p->mfMinDistance = min_dist;
+        p->mNormalVector = Eigen::Vector3f(n[0], n[1], n[2]);
     }
     static void Track(MapPoint* p, TrackFields* t) {
         t->in_view = p->mbTrackInView;

@@ -34,7 +34,7 @@ class KeyFrame:
     """Keyframe data for the matcher.  feat_vec: dict node_id -> list of feature indices."""
 
     def __init__(self, keys_un, descriptors, Tcw, camera, scale_factors, level_sigma2, u_right=None,
-                 has_mappoint=None, feat_vec=None):
+                 has_mappoint=None, feat_vec=None, Ow=None, mb=0.0, mbf=0.0, depth=None, keys_raw=None):
         self.mvKeysUn = np.ascontiguousarray(keys_un, dtype=KEYPOINT_DTYPE)
         self.N = len(self.mvKeysUn)
         self.mDescriptors = np.ascontiguousarray(descriptors, dtype=np.uint8).reshape(self.N, 32)
@@ -54,6 +54,12 @@ class KeyFrame:
             self.fv_offset[i + 1] = len(idx)
         self.fv_index = np.asarray(idx, dtype=np.int32)
         self._view = None
+        # what CreateNewMapPoints' triangulation reads besides the above (newpoints_view): GetCameraCenter()
+        # (None: -Rcw^T tcw in float32), mb, mbf, mvDepth (None: monocular), mvKeys (None: mvKeysUn)
+        self.Ow = None if Ow is None else np.ascontiguousarray(Ow, dtype=np.float32).reshape(3)
+        self.mb, self.mbf = float(np.float32(mb)), float(np.float32(mbf))
+        self.mvDepth = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32).reshape(self.N)
+        self.mvKeys = None if keys_raw is None else np.ascontiguousarray(keys_raw, dtype=KEYPOINT_DTYPE).reshape(self.N)
 
     @property
     def mFeatVec(self) -> dict:
@@ -67,6 +73,59 @@ class KeyFrame:
                                 _ptr(self.fv_index), self.fx, self.fy, self.cx, self.cy, len(self.mvScaleFactors),
                                 _ptr(self.mvScaleFactors), _ptr(self.mvLevelSigma2))
         return self._view
+
+    def newpoints_view(self) -> "NewPointsKf":
+        """orb_newpoints_kf_t of this keyframe (ORBmatcher.CreateNewMapPoints)."""
+        v = NewPointsKf()
+        ctypes.memmove(ctypes.byref(v.view), ctypes.byref(self.view()), ctypes.sizeof(KfView))
+        v.extra = newpoints_extra(self, _ptr(self.mvDepth), _ptr(self.mvKeys))
+        return v
+
+
+class NewPointsKfExtra(ctypes.Structure):  # orb_newpoints_kf_extra_t
+    _fields_ = [("Tcw", ctypes.c_float * 12), ("Ow", ctypes.c_float * 3), ("mb", ctypes.c_float), ("mbf", ctypes.c_float),
+                ("invfx", ctypes.c_float), ("invfy", ctypes.c_float), ("depth", ctypes.c_void_p),
+                ("kps_raw", ctypes.c_void_p)]
+
+
+def newpoints_extra(kf, depth_ptr, kps_raw_ptr) -> NewPointsKfExtra:
+    """The extra fields of a KeyFrame / DeviceKeyFrame; invfx = 1.0f / fx as src/Frame.cc has it."""
+    if kf.Ow is None:
+        kf.Ow = np.ascontiguousarray(-(kf.Tcw[:, :3].T @ kf.Tcw[:, 3]), dtype=np.float32)
+    e = NewPointsKfExtra()
+    e.Tcw[:] = [float(x) for x in kf.Tcw.reshape(-1)]
+    e.Ow[:] = [float(x) for x in kf.Ow]
+    e.mb, e.mbf = kf.mb, kf.mbf
+    e.invfx = float(np.float32(1.0) / np.float32(kf.fx))
+    e.invfy = float(np.float32(1.0) / np.float32(kf.fy))
+    e.depth, e.kps_raw = depth_ptr, kps_raw_ptr
+    return e
+
+
+class NewPointsKf(ctypes.Structure):  # orb_newpoints_kf_t
+    _fields_ = [("view", KfView), ("extra", NewPointsKfExtra)]
+
+
+class NewPointsParams(ctypes.Structure):  # orb_newpoints_params_t
+    _fields_ = [("inertial", ctypes.c_int32), ("far_points", ctypes.c_int32), ("th_far_points", ctypes.c_float),
+                ("ratio_factor", ctypes.c_float)]
+
+
+class NewPointsOut(ctypes.Structure):  # orb_newpoints_out_t
+    _fields_ = [("status", ctypes.c_void_p), ("x3d", ctypes.c_void_p), ("from_stereo", ctypes.c_void_p),
+                ("taken_by", ctypes.c_void_p), ("records", ctypes.c_void_p), ("n_new", ctypes.c_void_p)]
+
+
+# orb_newpoint_t (48 bytes)
+NEWPOINT_DTYPE = np.dtype([("p", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("x3d", "<f4", 3), ("from_stereo", "<i4"),
+                           ("normal", "<f4", 3), ("min_dist", "<f4"), ("max_dist", "<f4")])
+assert NEWPOINT_DTYPE.itemsize == 48
+
+# the status codes of CreateNewMapPoints (ORB_NP_* of include/orbgpu.h)
+NP_STATUS = ("NO_MATCH", "LOW_PARALLAX", "TRI_W_ZERO", "STEREO_DEPTH", "Z1", "Z2", "CHI2_1", "CHI2_2", "DIST_ZERO", "FAR",
+             "SCALE", "OK", "TAKEN")
+(NP_NO_MATCH, NP_LOW_PARALLAX, NP_TRI_W_ZERO, NP_STEREO_DEPTH, NP_Z1, NP_Z2, NP_CHI2_1, NP_CHI2_2, NP_DIST_ZERO, NP_FAR,
+ NP_SCALE, NP_OK, NP_TAKEN) = range(13)
 
 
 class KfDeviceView(ctypes.Structure):  # orb_kf_device_t
@@ -84,9 +143,13 @@ class DeviceKeyFrame:
     geometry needs.  has_mappoint: optional [B, cap] uint8 CUDA tensor."""
 
     def __init__(self, extracted, bow, f: int, Tcw, camera, scale_factors, level_sigma2, u_right=None,
-                 has_mappoint=None):
+                 has_mappoint=None, Ow=None, mb=0.0, mbf=0.0, depth=None, kps_raw=None):
         kps, desc, counts = extracted
-        self._keep = (kps, desc, counts, bow, u_right, has_mappoint)
+        self._keep = (kps, desc, counts, bow, u_right, has_mappoint, depth, kps_raw)
+        # CreateNewMapPointsDevice's extra fields: depth [B, cap] float32 (mvDepth, e.g. of
+        # compute_stereo_matches_batch_device), kps_raw [B, cap, 7] float32 (mvKeys; None: kps), Ow, mb, mbf
+        self.Ow = None if Ow is None else np.ascontiguousarray(Ow, dtype=np.float32).reshape(3)
+        self.mb, self.mbf = float(np.float32(mb)), float(np.float32(mbf))
         self.cap = int(kps.shape[1])
         self.f = int(f)
         self.Tcw = np.ascontiguousarray(Tcw, dtype=np.float32).reshape(3, 4)
@@ -105,6 +168,19 @@ class DeviceKeyFrame:
 
     def view(self) -> KfDeviceView:
         return self._view
+
+    def newpoints_view(self) -> "NewPointsKfDevice":
+        """orb_newpoints_kf_device_t of this keyframe (ORBmatcher.CreateNewMapPointsDevice)."""
+        depth, raw = self._keep[6], self._keep[7]
+        v = NewPointsKfDevice()
+        ctypes.memmove(ctypes.byref(v.view), ctypes.byref(self._view), ctypes.sizeof(KfDeviceView))
+        v.extra = newpoints_extra(self, None if depth is None else depth.data_ptr() + 4 * self.cap * self.f,
+                                  None if raw is None else raw.data_ptr() + 28 * self.cap * self.f)
+        return v
+
+
+class NewPointsKfDevice(ctypes.Structure):  # orb_newpoints_kf_device_t
+    _fields_ = [("view", KfDeviceView), ("extra", NewPointsKfExtra)]
 
 
 class FrameView(ctypes.Structure):

@@ -7,8 +7,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .keyframe import (DeviceKeyFrame, Frame, FuseKfView, FusePoints, FusePointsView, KeyFrame, KfDeviceView, KfView,
-                       LocalMapPoints, PairGeom)
+from .keyframe import (NEWPOINT_DTYPE, DeviceKeyFrame, Frame, FuseKfView, FusePoints, FusePointsView, KeyFrame,
+                       KfDeviceView, KfView, LocalMapPoints, NewPointsKf, NewPointsKfDevice, NewPointsOut,
+                       NewPointsParams, PairGeom)
 
 TH_HIGH = 100  # src/ORBmatcher.cc:36
 TH_LOW = 50    # src/ORBmatcher.cc:37
@@ -227,6 +228,84 @@ class ORBmatcher:
                                           float(th), out[0].data_ptr(), out[1].data_ptr(),
                                           ctypes.c_void_p(st.cuda_stream)), "orb_fuse_device")
         return out[0][:K, :n], out[1][:K, :n]
+
+    @staticmethod
+    def _newpoints_params(pKF1, inertial, far_points, th_far_points, ratio_factor) -> NewPointsParams:
+        if ratio_factor is None:  # 1.5f * mfScaleFactor (src/LocalMapping.cc:555)
+            ratio_factor = np.float32(1.5) * pKF1.mvScaleFactors[1] if len(pKF1.mvScaleFactors) > 1 else 1.5
+        return NewPointsParams(int(bool(inertial)), int(bool(far_points)), float(np.float32(th_far_points)),
+                               float(np.float32(ratio_factor)))
+
+    def CreateNewMapPoints(self, pKF1: KeyFrame, neighbours, matches12, n_matches=None, inertial: bool = False,
+                           far_points: bool = False, th_far_points: float = 0.0, ratio_factor=None) -> dict:
+        """The triangulation half of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:626-910) for the
+        matches of pKF1 against every keyframe of `neighbours` in one call: matches12 [P, N1] (and n_matches [P],
+        optional) as SearchForTriangulationMany returned them.  Returns a dict: status [P, N1] int32 (NP_* of
+        keyframe.py), x3d [P, N1, 3], from_stereo [P, N1] uint8, taken_by [N1] int32 and `new`, the records of
+        the new map points (NEWPOINT_DTYPE) in upstream's creation order.  Step 6, the map mutation, is the
+        caller's."""
+        neighbours = list(neighbours)
+        P, n1 = len(neighbours), pKF1.N
+        C = max(n1, 1)
+        m12 = np.full((max(P, 1), C), -1, np.int32)
+        if P and n1:
+            m12[:P, :n1] = np.asarray(matches12, np.int32).reshape(P, n1)
+        cnt = None if n_matches is None else np.ascontiguousarray(n_matches, dtype=np.int32).reshape(P)
+        status = np.zeros((max(P, 1), C), np.int32)
+        x3d = np.zeros((max(P, 1), C, 3), np.float32)
+        fs = np.zeros((max(P, 1), C), np.uint8)
+        taken = np.full(C, -1, np.int32)
+        rec = np.zeros(C, NEWPOINT_DTYPE)
+        n_new = np.zeros(1, np.int32)
+        out = NewPointsOut(status.ctypes.data, x3d.ctypes.data, fs.ctypes.data, taken.ctypes.data, rec.ctypes.data,
+                           n_new.ctypes.data)
+        v1 = pKF1.newpoints_view()
+        v2 = (NewPointsKf * max(P, 1))(*[k.newpoints_view() for k in neighbours])
+        prm = self._newpoints_params(pKF1, inertial, far_points, th_far_points, ratio_factor)
+        check(_lib.load().orb_create_new_map_points(self._handle(), ctypes.byref(v1), v2, P, ctypes.byref(prm),
+                                                    m12.ctypes.data, None if cnt is None else cnt.ctypes.data,
+                                                    ctypes.byref(out)), "orb_create_new_map_points")
+        return dict(status=status[:P, :n1], x3d=x3d[:P, :n1], from_stereo=fs[:P, :n1], taken_by=taken[:n1],
+                    new=rec[:int(n_new[0])])
+
+    def CreateNewMapPointsDevice(self, pKF1: DeviceKeyFrame, neighbours, matches12, n_matches, inertial: bool = False,
+                                 far_points: bool = False, th_far_points: float = 0.0, ratio_factor=None, stream=None,
+                                 out=None) -> dict:
+        """The same on device-resident keyframes (orb_create_new_map_points_device), asynchronous on `stream`
+        with no host synchronisation: matches12 [P, cap1] / n_matches [P] are the CUDA tensors
+        SearchForTriangulationDevice(pKF1, neighbours, ...) returned, taken as they are (a pair flagged
+        ORB_ERR_CAPACITY yields no points).  Returns a dict of CUDA tensors -- status [P, cap1] int32, x3d
+        [P, cap1, 3] float32, from_stereo [P, cap1] uint8, taken_by [cap1] int32, records [cap1, 12] int32 (the
+        bytes of NEWPOINT_DTYPE; newpoints_records() decodes a downloaded copy), n_new [1] int32 -- which `out`
+        (an earlier call's dict) reuses."""
+        import torch
+        neighbours = list(neighbours)
+        P, C = len(neighbours), pKF1.cap
+        dev = pKF1._keep[0].device
+        if out is None:
+            out = dict(status=torch.empty((max(P, 1), C), dtype=torch.int32, device=dev),
+                       x3d=torch.empty((max(P, 1), C, 3), dtype=torch.float32, device=dev),
+                       from_stereo=torch.empty((max(P, 1), C), dtype=torch.uint8, device=dev),
+                       taken_by=torch.empty(C, dtype=torch.int32, device=dev),
+                       records=torch.empty((C, 12), dtype=torch.int32, device=dev),
+                       n_new=torch.empty(1, dtype=torch.int32, device=dev))
+        o = NewPointsOut(*[out[k].data_ptr() for k in ("status", "x3d", "from_stereo", "taken_by", "records", "n_new")])
+        v1 = pKF1.newpoints_view()
+        v2 = (NewPointsKfDevice * max(P, 1))(*[k.newpoints_view() for k in neighbours])
+        prm = self._newpoints_params(pKF1, inertial, far_points, th_far_points, ratio_factor)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        check(_lib.load().orb_create_new_map_points_device(self._handle(), ctypes.byref(v1), v2, P, ctypes.byref(prm),
+                                                           matches12.data_ptr(),
+                                                           None if n_matches is None else n_matches.data_ptr(),
+                                                           ctypes.byref(o), ctypes.c_void_p(st.cuda_stream)),
+              "orb_create_new_map_points_device")
+        return out
+
+    @staticmethod
+    def newpoints_records(records, n_new) -> np.ndarray:
+        """The first n_new records of CreateNewMapPointsDevice's `records` tensor as NEWPOINT_DTYPE (a download)."""
+        n = int(n_new.item()) if hasattr(n_new, "item") else int(n_new)
+        return np.ascontiguousarray(records.cpu().numpy()).view(NEWPOINT_DTYPE).reshape(-1)[:n]
 
     @staticmethod
     def DescriptorDistance(a, b) -> int:
