@@ -5,9 +5,12 @@
 // with observations, later last-frame points skip it (src:2050-2052).  Everything else -- the
 // projection, the grid window, the level range, the stereo check, the Hamming distances -- is
 // independent per point, so:
-//   k_proj_candidates  one thread per last-frame point: project, walk the 64 x 48 grid window in the
-//                      reference's cell order and keep (keypoint, distance) of every candidate that
-//                      passes the static tests, plus the first minimum (the unconstrained best).
+//   k_proj_candidates  per last-frame point: project, walk the 64 x 48 grid window in the reference's
+//                      cell order and keep (keypoint, distance) of every candidate that passes the
+//                      static tests.  Three forms write the same lists: one wave per point (host and
+//                      single device calls), and for the tracking chain's batches one thread per point
+//                      with the frame's records staged in LDS (_l_b) or, when they do not fit, read
+//                      from global memory (_t_b).
 //   k_lmp_candidates   the same for SearchByProjection(Frame, local map points) (src:46-240).
 //   k_resolve_rounds   one workgroup: the in-order assignment of both overloads (ratio test for the
 //                      local map), decided in parallel rounds (below), then the rotation histogram /
@@ -20,13 +23,19 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
 #include <vector>
-#include <cstdlib>
 
 #include "orbgpu.h"
 #include "orb_frame_grid.h"
 #include "orb_rot_hist.h"
 #include "orbgpu_internal.h"
+
+// Defined in orb_triangulation.hip: the matcher handle's staging buffers and ratio.
+int orbgpu_matcher_reserve(orb_matcher_t m, size_t bytes, char** d_buf, char** h_buf, hipStream_t* stream,
+                           int* check_ori);
+float orbgpu_matcher_nnratio(orb_matcher_t m);
+int orbgpu_matcher_check_ori(orb_matcher_t m);
 
 namespace {
 
@@ -40,19 +49,163 @@ struct ProjParams {
     int n_cur, n_last, has_ur, bForward, bBackward, cap, check_ori;
 };
 
+// SearchByProjection(Frame&, vector<MapPoint*>, th, bFarPoints, thFarPoints), src:46-240
+struct LocalParams {
+    float min_x, min_y, inv_w, inv_h, th, th_far, nnratio;
+    float scale[kMaxLevels];
+    int n_cur, n_pts, has_ur, far, nlevels, cap;
+};
+
 struct Cand {
     int32_t i2;
     int32_t dist;
 };
 
-// After a point's candidates are written: the wave (lanes over its list) records, for every usable
-// candidate keypoint (distance < 256, not already taken), the earliest observed point listing it
-// (`lister`, initialised to 0x7f7f7f7f).  k_resolve_init uses it to find the points whose answer no
-// earlier point can change.
-__device__ __forceinline__ void record_listers(int lane, int i, int n, int cap, const Cand* __restrict__ c_i,
+// The current frame's records as the window walkers and the candidate test read them: global
+// pointers, or in the LDS-staged form orb_frame_grid.h's address-space-3 readers.
+template <class KP = const float4*, class UR = const float*, class DS = const uint4*, class CO = const int32_t*,
+          class CI = const int32_t*>
+struct CurRecords {
+    KP kp;  // x, y, angle, octave bits
+    UR ur;
+    DS desc;
+    CO cell_off;
+    CI cell_idx;
+};
+
+// The argument blocks of the candidate kernels (by value for a single call, one per frame on the
+// device for a batch).
+struct k_proj_candidates_args {
+    ProjParams P;
+    const int32_t* n_dev;  // device forms: the point count the prep kernel clamped (NULL: P.n_last)
+    const uint8_t* valid;
+    const float* xyz;
+    const uint4* mp_desc;
+    const int32_t* last_octave;
+    CurRecords<> cur;
+    Cand* cands;
+    int32_t* ncand;
+    int32_t* overflow;
+    const uint8_t* observed;
+    int32_t* lister;
+};
+struct k_lmp_candidates_args {
+    LocalParams P;
+    const uint8_t* in_view;
+    const uint8_t* bad;
+    const float* proj;
+    const float* view_cos;
+    const float* depth;
+    const int32_t* level;
+    const uint4* mp_desc;
+    CurRecords<> cur;
+    Cand* cands;
+    int32_t* ncand;
+    int32_t* overflow;
+    const uint8_t* observed;
+    const uint8_t* taken0;
+    int32_t* lister;
+};
+__device__ __forceinline__ int n_points(const k_proj_candidates_args& A) { return A.n_dev ? *A.n_dev : A.P.n_last; }
+__device__ __forceinline__ int n_points(const k_lmp_candidates_args& A) { return A.P.n_pts; }
+__device__ __forceinline__ const uint8_t* taken0(const k_proj_candidates_args&) { return nullptr; }
+__device__ __forceinline__ const uint8_t* taken0(const k_lmp_candidates_args& A) { return A.taken0; }
+
+// A point's search: the grid cells x0..x1, y0..y1 around (u, v), the radius, the right-image
+// coordinate, the octave range (maxLevel < 0: open) and the point's descriptor.
+struct Window {
+    int x0, x1, y0, y1;
+    float u, v, radius, ur;
+    int minLevel, maxLevel;
+    uint4 d0, d1;
+};
+
+// The cells of (u, v) +- radius (Frame::GetFeaturesInArea, src/Frame.cc:865-885) and the point's
+// descriptor; false when the window holds no cell.
+template <class Params>
+__device__ __forceinline__ bool open_window(const Params& P, const uint4* __restrict__ mp_desc, int i, Window& W) {
+    W.x0 = max(0, (int)floorf((W.u - P.min_x - W.radius) * P.inv_w));
+    W.x1 = min(kGridCols - 1, (int)ceilf((W.u - P.min_x + W.radius) * P.inv_w));
+    W.y0 = max(0, (int)floorf((W.v - P.min_y - W.radius) * P.inv_h));
+    W.y1 = min(kGridRows - 1, (int)ceilf((W.v - P.min_y + W.radius) * P.inv_h));
+    if (!(W.x0 < kGridCols && W.x1 >= 0 && W.y0 < kGridRows && W.y1 >= 0)) return false;
+    W.d0 = mp_desc[2 * (size_t)i];
+    W.d1 = mp_desc[2 * (size_t)i + 1];
+    return true;
+}
+
+// Last-frame point i (src:1978-2037): project with the current pose, the radius of its octave, the
+// levels by forward / backward motion (src:2019-2024).  False: the point searches nothing.
+__device__ __forceinline__ bool point_window(const k_proj_candidates_args& A, int i, Window& W) {
+    const ProjParams& P = A.P;
+    if (!A.valid[i]) return false;
+    const float x = A.xyz[3 * i], y = A.xyz[3 * i + 1], z = A.xyz[3 * i + 2];
+    float c[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        c[r] = __fmaf_rn(P.Tcw[4 * r + 2], z, __fmaf_rn(P.Tcw[4 * r], x, P.Tcw[4 * r + 1] * y)) + P.Tcw[4 * r + 3];
+    const float invzc = (float)(1.0 / (double)c[2]);
+    W.u = P.fx * c[0] / c[2] + P.cx;
+    W.v = P.fy * c[1] / c[2] + P.cy;
+    if (invzc < 0 || W.u < P.min_x || W.u > P.max_x || W.v < P.min_y || W.v > P.max_y) return false;
+    const int oct = A.last_octave[i];
+    W.radius = P.th * P.scale[oct];
+    if (P.bForward) { W.minLevel = oct; W.maxLevel = -1; }
+    else if (P.bBackward) { W.minLevel = 0; W.maxLevel = oct; }
+    else { W.minLevel = oct - 1; W.maxLevel = oct + 1; }
+    W.ur = __fmaf_rn(-P.bf, invzc, W.u);
+    return open_window(P, A.mp_desc, i, W);
+}
+
+// Local map point i (src:54-95): in view, not far, not bad; RadiusByViewingCos at the predicted
+// level, levels level-1 .. level.
+__device__ __forceinline__ bool point_window(const k_lmp_candidates_args& A, int i, Window& W) {
+    const LocalParams& P = A.P;
+    if (!(A.in_view[i] && !(P.far && A.depth[i] > P.th_far) && !A.bad[i])) return false;
+    const int lvl = A.level[i];
+    float r = ((double)A.view_cos[i] > 0.998) ? 2.5f : 4.0f;  // RadiusByViewingCos (src:243-250)
+    if (P.th != 1.0f) r *= P.th;
+    W.radius = r * P.scale[lvl];
+    W.u = A.proj[3 * i];
+    W.v = A.proj[3 * i + 1];
+    W.ur = A.proj[3 * i + 2];
+    W.minLevel = lvl - 1;
+    W.maxLevel = lvl;
+    return open_window(P, A.mp_desc, i, W);
+}
+
+// The static tests of keypoint j against a window (src:107-124, :2044-2055): the level range,
+// |dx|, |dy| < radius, the stereo u_R gate.  The Hamming distance, or -1 when j is no candidate.
+template <class Cur>
+struct CandTest {
+    const Window& W;
+    const int has_ur;
+    const Cur& cur;
+    __device__ __forceinline__ int operator()(int j) const {
+        const float4 kp = cur.kp[j];
+        const int koct = __float_as_int(kp.w);
+        if (W.minLevel > 0 || W.maxLevel >= 0) {  // bCheckLevels
+            if (koct < W.minLevel) return -1;
+            if (W.maxLevel >= 0 && koct > W.maxLevel) return -1;
+        }
+        const float distx = kp.x - W.u, disty = kp.y - W.v;
+        if (!(fabsf(distx) < W.radius && fabsf(disty) < W.radius)) return -1;
+        if (has_ur && cur.ur[j] > 0) {
+            const float er = fabsf(W.ur - cur.ur[j]);
+            if (er > W.radius) return -1;
+        }
+        return hamming(W.d0, W.d1, cur.desc[2 * (size_t)j], cur.desc[2 * (size_t)j + 1]);
+    }
+};
+
+// After a point's candidates are written: its wave (lanes over the list: first = lane, stride 64) or
+// its thread (first 0, stride 1) records, for every usable candidate keypoint (distance < 256, not
+// already taken), the earliest observed point listing it (`lister`, initialised to 0x7f7f7f7f).
+// k_resolve_init uses it to find the points whose answer no earlier point can change.
+__device__ __forceinline__ void record_listers(int first, int stride, int i, int n, int cap, const Cand* __restrict__ c_i,
                                                const uint8_t* __restrict__ taken0, int32_t* __restrict__ lister) {
     if (n > cap) return;  // overflow: the call is redone with a larger capacity
-    for (int k = lane; k < n; k += 64) {
+    for (int k = first; k < n; k += stride) {
         const Cand c = c_i[k];
         if (c.dist < 256 && !(taken0 && taken0[c.i2])) atomicMin(&lister[c.i2], i);
     }
@@ -114,118 +267,11 @@ __device__ __forceinline__ int window_candidates(int lane, int* __restrict__ pre
     return n;
 }
 
-constexpr int kCandWaves = 4;
-
-// one wave per last-frame point (src:1978-2062 up to the minimum): project with the current pose,
-// the window by forward / backward motion (src:2019-2024), the stereo u_R test, distances
-__device__ __forceinline__ void k_proj_candidates_body(const ProjParams P, const int32_t* __restrict__ n_dev,
-                                                         const uint8_t* __restrict__ valid,
-                                                         const float* __restrict__ xyz, const uint4* __restrict__ mp_desc,
-                                                         const int32_t* __restrict__ last_octave,
-                                                         const float4* __restrict__ cur_kp,  // x, y, angle, octave bits
-                                                         const float* __restrict__ cur_ur, const uint4* __restrict__ cur_desc,
-                                                         const int32_t* __restrict__ cell_off, const int32_t* __restrict__ cell_idx,
-                                                         Cand* __restrict__ cands, int32_t* __restrict__ ncand,
-                                                         int32_t* __restrict__ overflow, const uint8_t* __restrict__ observed,
-                                                         int32_t* __restrict__ lister) {
-    __shared__ int pre_s[kCandWaves][64], beg_s[kCandWaves][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int i = blockIdx.x * kCandWaves + w;
-    if (i >= (n_dev ? *n_dev : P.n_last)) return;  // (device forms: the count the prep kernel clamped)
-    int n = 0;
-    if (valid[i]) {
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        float c[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            c[r] = __fmaf_rn(P.Tcw[4 * r + 2], z, __fmaf_rn(P.Tcw[4 * r], x, P.Tcw[4 * r + 1] * y)) + P.Tcw[4 * r + 3];
-        const float invzc = (float)(1.0 / (double)c[2]);
-        const float u = P.fx * c[0] / c[2] + P.cx;
-        const float v = P.fy * c[1] / c[2] + P.cy;
-        if (!(invzc < 0) && !(u < P.min_x || u > P.max_x || v < P.min_y || v > P.max_y)) {
-            const int oct = last_octave[i];
-            const float radius = P.th * P.scale[oct];
-            int minLevel, maxLevel;
-            if (P.bForward) { minLevel = oct; maxLevel = -1; }
-            else if (P.bBackward) { minLevel = 0; maxLevel = oct; }
-            else { minLevel = oct - 1; maxLevel = oct + 1; }
-            const int x0 = max(0, (int)floorf((u - P.min_x - radius) * P.inv_w));
-            const int x1 = min(kGridCols - 1, (int)ceilf((u - P.min_x + radius) * P.inv_w));
-            const int y0 = max(0, (int)floorf((v - P.min_y - radius) * P.inv_h));
-            const int y1 = min(kGridRows - 1, (int)ceilf((v - P.min_y + radius) * P.inv_h));
-            if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-                const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-                const uint4 d0 = mp_desc[2 * (size_t)i], d1 = mp_desc[2 * (size_t)i + 1];
-                const float ur = __fmaf_rn(-P.bf, invzc, u);
-                n = window_candidates(lane, pre_s[w], beg_s[w], cell_off, cell_idx, x0, x1, y0, y1,
-                                      cands + (size_t)i * P.cap, P.cap, [&](int j) -> int {
-                                          const float4 kp = cur_kp[j];
-                                          const int koct = __float_as_int(kp.w);
-                                          if (bCheckLevels) {
-                                              if (koct < minLevel) return -1;
-                                              if (maxLevel >= 0 && koct > maxLevel) return -1;
-                                          }
-                                          const float distx = kp.x - u, disty = kp.y - v;
-                                          if (!(fabsf(distx) < radius && fabsf(disty) < radius)) return -1;
-                                          if (P.has_ur && cur_ur[j] > 0) {
-                                              const float er = fabsf(ur - cur_ur[j]);
-                                              if (er > radius) return -1;
-                                          }
-                                          return hamming(d0, d1, cur_desc[2 * (size_t)j], cur_desc[2 * (size_t)j + 1]);
-                                      });
-            }
-        }
-    }
-    if (lane == 0) {
-        ncand[i] = n;
-        if (n > P.cap) atomicMax(overflow, n);
-    }
-    __threadfence_block();  // the wave's own candidate stores, read back across lanes
-    if (observed[i]) record_listers(lane, i, n, P.cap, cands + (size_t)i * P.cap, nullptr, lister);
-}
-__global__ __launch_bounds__(64 * kCandWaves) void k_proj_candidates(const ProjParams P, const int32_t* __restrict__ n_dev,
-                                                         const uint8_t* __restrict__ valid,
-                                                         const float* __restrict__ xyz, const uint4* __restrict__ mp_desc,
-                                                         const int32_t* __restrict__ last_octave,
-                                                         const float4* __restrict__ cur_kp,  // x, y, angle, octave bits
-                                                         const float* __restrict__ cur_ur, const uint4* __restrict__ cur_desc,
-                                                         const int32_t* __restrict__ cell_off, const int32_t* __restrict__ cell_idx,
-                                                         Cand* __restrict__ cands, int32_t* __restrict__ ncand,
-                                                         int32_t* __restrict__ overflow, const uint8_t* __restrict__ observed,
-                                                         int32_t* __restrict__ lister) {
-    k_proj_candidates_body(P, n_dev, valid, xyz, mp_desc, last_octave, cur_kp, cur_ur, cur_desc, cell_off, cell_idx,
-                           cands, ncand, overflow, observed, lister);
-}
-struct k_proj_candidates_args {
-    ProjParams P;
-    const int32_t* n_dev;
-    const uint8_t* valid;
-    const float* xyz;
-    const uint4* mp_desc;
-    const int32_t* last_octave;
-    const float4* cur_kp;
-    const float* cur_ur;
-    const uint4* cur_desc;
-    const int32_t* cell_off;
-    const int32_t* cell_idx;
-    Cand* cands;
-    int32_t* ncand;
-    int32_t* overflow;
-    const uint8_t* observed;
-    int32_t* lister;
-};
-// the same on frame blockIdx.y of a batch (one argument block per frame)
-__global__ __launch_bounds__(64 * kCandWaves) void k_proj_candidates_b(const k_proj_candidates_args* __restrict__ a) {
-    const k_proj_candidates_args& A = a[blockIdx.y];
-    k_proj_candidates_body(A.P, A.n_dev, A.valid, A.xyz, A.mp_desc, A.last_octave, A.cur_kp, A.cur_ur, A.cur_desc,
-                           A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.lister);
-}
-
 // The same candidate lists with one THREAD per point (round 5): a window holds a handful of cells and
 // keypoints, so a wave per point spent most of its time on the 64-lane prefix and compaction machinery;
 // a thread walks its window's cells (ix outer, iy inner) and their keypoints in index order, which is
 // window_candidates' order, and writes the same list.
-template <class Test, class CO = const int32_t*, class CI = const int32_t*>
+template <class Test, class CO, class CI>
 __device__ __forceinline__ int window_candidates_serial(CO cell_off, CI cell_idx, int x0, int x1, int y0,
                                                         int y1, Cand* __restrict__ out, int cap, Test test) {
     int n = 0;
@@ -244,252 +290,62 @@ __device__ __forceinline__ int window_candidates_serial(CO cell_off, CI cell_idx
         }
     return n;
 }
-__device__ __forceinline__ void record_listers_serial(int i, int n, int cap, const Cand* __restrict__ c_i,
-                                                      const uint8_t* __restrict__ taken0, int32_t* __restrict__ lister) {
-    if (n > cap) return;  // overflow: the call is redone with a larger capacity
-    for (int k = 0; k < n; ++k) {
-        const Cand c = c_i[k];
-        if (c.dist < 256 && !(taken0 && taken0[c.i2])) atomicMin(&lister[c.i2], i);
-    }
-}
 
+constexpr int kCandWaves = 4;
 constexpr int kCandThreads = 256;
 
-// (KP / UR / DS / CO / CI: the current frame's records, global pointers or, in the LDS-staged form, LDS ones)
-template <class KP = const float4*, class UR = const float*, class DS = const uint4*, class CO = const int32_t*,
-          class CI = const int32_t*>
-__device__ __forceinline__ void k_proj_candidates_t_body(int i, const ProjParams P, const int32_t* __restrict__ n_dev,
-                                                         const uint8_t* __restrict__ valid,
-                                                         const float* __restrict__ xyz, const uint4* __restrict__ mp_desc,
-                                                         const int32_t* __restrict__ last_octave,
-                                                         KP cur_kp, UR cur_ur, DS cur_desc, CO cell_off, CI cell_idx,
-                                                         Cand* __restrict__ cands, int32_t* __restrict__ ncand,
-                                                         int32_t* __restrict__ overflow, const uint8_t* __restrict__ observed,
-                                                         int32_t* __restrict__ lister) {
-    if (i >= (n_dev ? *n_dev : P.n_last)) return;
+// One wave per point, both overloads (src:54-143 / :1978-2062 up to the minima).  pre / beg: the
+// wave's 64-entry prefix arrays in LDS.
+template <class Args>
+__device__ __forceinline__ void candidates_wave(const Args& A, int* pre, int* beg) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * kCandWaves + (threadIdx.x >> 6);
+    if (i >= n_points(A)) return;
+    Cand* const out = A.cands + (size_t)i * A.P.cap;
+    Window W;
     int n = 0;
-    Cand* const out = cands + (size_t)i * P.cap;
-    if (valid[i]) {
-        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-        float c[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-            c[r] = __fmaf_rn(P.Tcw[4 * r + 2], z, __fmaf_rn(P.Tcw[4 * r], x, P.Tcw[4 * r + 1] * y)) + P.Tcw[4 * r + 3];
-        const float invzc = (float)(1.0 / (double)c[2]);
-        const float u = P.fx * c[0] / c[2] + P.cx;
-        const float v = P.fy * c[1] / c[2] + P.cy;
-        if (!(invzc < 0) && !(u < P.min_x || u > P.max_x || v < P.min_y || v > P.max_y)) {
-            const int oct = last_octave[i];
-            const float radius = P.th * P.scale[oct];
-            int minLevel, maxLevel;
-            if (P.bForward) { minLevel = oct; maxLevel = -1; }
-            else if (P.bBackward) { minLevel = 0; maxLevel = oct; }
-            else { minLevel = oct - 1; maxLevel = oct + 1; }
-            const int x0 = max(0, (int)floorf((u - P.min_x - radius) * P.inv_w));
-            const int x1 = min(kGridCols - 1, (int)ceilf((u - P.min_x + radius) * P.inv_w));
-            const int y0 = max(0, (int)floorf((v - P.min_y - radius) * P.inv_h));
-            const int y1 = min(kGridRows - 1, (int)ceilf((v - P.min_y + radius) * P.inv_h));
-            if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-                const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-                const uint4 d0 = mp_desc[2 * (size_t)i], d1 = mp_desc[2 * (size_t)i + 1];
-                const float ur = __fmaf_rn(-P.bf, invzc, u);
-                n = window_candidates_serial(cell_off, cell_idx, x0, x1, y0, y1, out, P.cap, [&](int j) -> int {
-                    const float4 kp = cur_kp[j];
-                    const int koct = __float_as_int(kp.w);
-                    if (bCheckLevels) {
-                        if (koct < minLevel) return -1;
-                        if (maxLevel >= 0 && koct > maxLevel) return -1;
-                    }
-                    const float distx = kp.x - u, disty = kp.y - v;
-                    if (!(fabsf(distx) < radius && fabsf(disty) < radius)) return -1;
-                    if (P.has_ur && cur_ur[j] > 0) {
-                        const float er = fabsf(ur - cur_ur[j]);
-                        if (er > radius) return -1;
-                    }
-                    return hamming(d0, d1, cur_desc[2 * (size_t)j], cur_desc[2 * (size_t)j + 1]);
-                });
-            }
-        }
-    }
-    ncand[i] = n;
-    if (n > P.cap) atomicMax(overflow, n);
-    if (observed[i]) record_listers_serial(i, n, P.cap, out, nullptr, lister);
-}
-__global__ __launch_bounds__(kCandThreads) void k_proj_candidates_t(const k_proj_candidates_args A) {
-    k_proj_candidates_t_body(blockIdx.x * kCandThreads + threadIdx.x, A.P, A.n_dev, A.valid, A.xyz, A.mp_desc, A.last_octave, A.cur_kp, A.cur_ur, A.cur_desc,
-                             A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.lister);
-}
-__global__ __launch_bounds__(kCandThreads) void k_proj_candidates_t_b(const k_proj_candidates_args* __restrict__ a) {
-    const k_proj_candidates_args& A = a[blockIdx.y];
-    k_proj_candidates_t_body(blockIdx.x * kCandThreads + threadIdx.x, A.P, A.n_dev, A.valid, A.xyz, A.mp_desc, A.last_octave, A.cur_kp, A.cur_ur, A.cur_desc,
-                             A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.lister);
-}
-
-__device__ __forceinline__ int rot_bin(float a1, float a2) { return orb_rot_bin(a1, a2); }
-
-// ---- SearchByProjection(Frame&, vector<MapPoint*>, th, bFarPoints, thFarPoints), src:46-240 -------
-
-struct LocalParams {
-    float min_x, min_y, inv_w, inv_h, th, th_far, nnratio;
-    float scale[kMaxLevels];
-    int n_cur, n_pts, has_ur, far, nlevels, cap;
-};
-
-// one wave per local map point (src:54-143 up to the minima): RadiusByViewingCos, the window at the
-// predicted level (levels level-1 .. level), the stereo u_R test, distances
-__device__ __forceinline__ void k_lmp_candidates_body(const LocalParams P, const uint8_t* __restrict__ in_view,
-                                                        const uint8_t* __restrict__ bad, const float* __restrict__ proj,
-                                                        const float* __restrict__ view_cos, const float* __restrict__ depth,
-                                                        const int32_t* __restrict__ level, const uint4* __restrict__ mp_desc,
-                                                        const float4* __restrict__ cur_kp, const float* __restrict__ cur_ur,
-                                                        const uint4* __restrict__ cur_desc, const int32_t* __restrict__ cell_off,
-                                                        const int32_t* __restrict__ cell_idx, Cand* __restrict__ cands,
-                                                        int32_t* __restrict__ ncand, int32_t* __restrict__ overflow,
-                                                        const uint8_t* __restrict__ observed, const uint8_t* __restrict__ taken0,
-                                                        int32_t* __restrict__ lister) {
-    __shared__ int pre_s[kCandWaves][64], beg_s[kCandWaves][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int i = blockIdx.x * kCandWaves + w;
-    if (i >= P.n_pts) return;
-    int n = 0;
-    if (in_view[i] && !(P.far && depth[i] > P.th_far) && !bad[i]) {
-        const int lvl = level[i];
-        float r = ((double)view_cos[i] > 0.998) ? 2.5f : 4.0f;  // RadiusByViewingCos (src:243-250)
-        if (P.th != 1.0f) r *= P.th;
-        const float radius = r * P.scale[lvl];
-        const float x = proj[3 * i], y = proj[3 * i + 1], xr = proj[3 * i + 2];
-        const int minLevel = lvl - 1, maxLevel = lvl;
-        const int x0 = max(0, (int)floorf((x - P.min_x - radius) * P.inv_w));
-        const int x1 = min(kGridCols - 1, (int)ceilf((x - P.min_x + radius) * P.inv_w));
-        const int y0 = max(0, (int)floorf((y - P.min_y - radius) * P.inv_h));
-        const int y1 = min(kGridRows - 1, (int)ceilf((y - P.min_y + radius) * P.inv_h));
-        if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-            const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-            const uint4 d0 = mp_desc[2 * (size_t)i], d1 = mp_desc[2 * (size_t)i + 1];
-            n = window_candidates(lane, pre_s[w], beg_s[w], cell_off, cell_idx, x0, x1, y0, y1, cands + (size_t)i * P.cap,
-                                  P.cap, [&](int j) -> int {
-                                      const float4 kp = cur_kp[j];
-                                      const int koct = __float_as_int(kp.w);
-                                      if (bCheckLevels) {
-                                          if (koct < minLevel) return -1;
-                                          if (maxLevel >= 0 && koct > maxLevel) return -1;
-                                      }
-                                      if (!(fabsf(kp.x - x) < radius && fabsf(kp.y - y) < radius)) return -1;
-                                      if (P.has_ur && cur_ur[j] > 0) {
-                                          const float er = fabsf(xr - cur_ur[j]);
-                                          if (er > r * P.scale[lvl]) return -1;
-                                      }
-                                      return hamming(d0, d1, cur_desc[2 * (size_t)j], cur_desc[2 * (size_t)j + 1]);
-                                  });
-        }
-    }
+    if (point_window(A, i, W))
+        n = window_candidates(lane, pre, beg, A.cur.cell_off, A.cur.cell_idx, W.x0, W.x1, W.y0, W.y1, out, A.P.cap,
+                              CandTest<CurRecords<>>{W, A.P.has_ur, A.cur});
     if (lane == 0) {
-        ncand[i] = n;
-        if (n > P.cap) atomicMax(overflow, n);
+        A.ncand[i] = n;
+        if (n > A.P.cap) atomicMax(A.overflow, n);
     }
     __threadfence_block();  // the wave's own candidate stores, read back across lanes
-    if (observed[i]) record_listers(lane, i, n, P.cap, cands + (size_t)i * P.cap, taken0, lister);
-}
-__global__ __launch_bounds__(64 * kCandWaves) void k_lmp_candidates(const LocalParams P, const uint8_t* __restrict__ in_view,
-                                                        const uint8_t* __restrict__ bad, const float* __restrict__ proj,
-                                                        const float* __restrict__ view_cos, const float* __restrict__ depth,
-                                                        const int32_t* __restrict__ level, const uint4* __restrict__ mp_desc,
-                                                        const float4* __restrict__ cur_kp, const float* __restrict__ cur_ur,
-                                                        const uint4* __restrict__ cur_desc, const int32_t* __restrict__ cell_off,
-                                                        const int32_t* __restrict__ cell_idx, Cand* __restrict__ cands,
-                                                        int32_t* __restrict__ ncand, int32_t* __restrict__ overflow,
-                                                        const uint8_t* __restrict__ observed, const uint8_t* __restrict__ taken0,
-                                                        int32_t* __restrict__ lister) {
-    k_lmp_candidates_body(P, in_view, bad, proj, view_cos, depth, level, mp_desc, cur_kp, cur_ur, cur_desc, cell_off,
-                          cell_idx, cands, ncand, overflow, observed, taken0, lister);
-}
-struct k_lmp_candidates_args {
-    LocalParams P;
-    const uint8_t* in_view;
-    const uint8_t* bad;
-    const float* proj;
-    const float* view_cos;
-    const float* depth;
-    const int32_t* level;
-    const uint4* mp_desc;
-    const float4* cur_kp;
-    const float* cur_ur;
-    const uint4* cur_desc;
-    const int32_t* cell_off;
-    const int32_t* cell_idx;
-    Cand* cands;
-    int32_t* ncand;
-    int32_t* overflow;
-    const uint8_t* observed;
-    const uint8_t* taken0;
-    int32_t* lister;
-};
-// the same on frame blockIdx.y of a batch (one argument block per frame)
-__global__ __launch_bounds__(64 * kCandWaves) void k_lmp_candidates_b(const k_lmp_candidates_args* __restrict__ a) {
-    const k_lmp_candidates_args& A = a[blockIdx.y];
-    k_lmp_candidates_body(A.P, A.in_view, A.bad, A.proj, A.view_cos, A.depth, A.level, A.mp_desc, A.cur_kp, A.cur_ur,
-                          A.cur_desc, A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.taken0,
-                          A.lister);
+    if (A.observed[i]) record_listers(lane, 64, i, n, A.P.cap, out, taken0(A), A.lister);
 }
 
-template <class KP = const float4*, class UR = const float*, class DS = const uint4*, class CO = const int32_t*,
-          class CI = const int32_t*>
-__device__ __forceinline__ void k_lmp_candidates_t_body(int i, const LocalParams P, const uint8_t* __restrict__ in_view,
-                                                        const uint8_t* __restrict__ bad, const float* __restrict__ proj,
-                                                        const float* __restrict__ view_cos, const float* __restrict__ depth,
-                                                        const int32_t* __restrict__ level, const uint4* __restrict__ mp_desc,
-                                                        KP cur_kp, UR cur_ur, DS cur_desc, CO cell_off, CI cell_idx,
-                                                        Cand* __restrict__ cands,
-                                                        int32_t* __restrict__ ncand, int32_t* __restrict__ overflow,
-                                                        const uint8_t* __restrict__ observed, const uint8_t* __restrict__ taken0,
-                                                        int32_t* __restrict__ lister) {
-    if (i >= P.n_pts) return;
+// One thread per point (point i), the current frame's records through `cur`.
+template <class Args, class Cur>
+__device__ __forceinline__ void candidates_thread(const Args& A, int i, const Cur& cur) {
+    if (i >= n_points(A)) return;
+    Cand* const out = A.cands + (size_t)i * A.P.cap;
+    Window W;
     int n = 0;
-    Cand* const out = cands + (size_t)i * P.cap;
-    if (in_view[i] && !(P.far && depth[i] > P.th_far) && !bad[i]) {
-        const int lvl = level[i];
-        float r = ((double)view_cos[i] > 0.998) ? 2.5f : 4.0f;  // RadiusByViewingCos (src:243-250)
-        if (P.th != 1.0f) r *= P.th;
-        const float radius = r * P.scale[lvl];
-        const float x = proj[3 * i], y = proj[3 * i + 1], xr = proj[3 * i + 2];
-        const int minLevel = lvl - 1, maxLevel = lvl;
-        const int x0 = max(0, (int)floorf((x - P.min_x - radius) * P.inv_w));
-        const int x1 = min(kGridCols - 1, (int)ceilf((x - P.min_x + radius) * P.inv_w));
-        const int y0 = max(0, (int)floorf((y - P.min_y - radius) * P.inv_h));
-        const int y1 = min(kGridRows - 1, (int)ceilf((y - P.min_y + radius) * P.inv_h));
-        if (x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0) {
-            const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-            const uint4 d0 = mp_desc[2 * (size_t)i], d1 = mp_desc[2 * (size_t)i + 1];
-            n = window_candidates_serial(cell_off, cell_idx, x0, x1, y0, y1, out, P.cap, [&](int j) -> int {
-                const float4 kp = cur_kp[j];
-                const int koct = __float_as_int(kp.w);
-                if (bCheckLevels) {
-                    if (koct < minLevel) return -1;
-                    if (maxLevel >= 0 && koct > maxLevel) return -1;
-                }
-                if (!(fabsf(kp.x - x) < radius && fabsf(kp.y - y) < radius)) return -1;
-                if (P.has_ur && cur_ur[j] > 0) {
-                    const float er = fabsf(xr - cur_ur[j]);
-                    if (er > r * P.scale[lvl]) return -1;
-                }
-                return hamming(d0, d1, cur_desc[2 * (size_t)j], cur_desc[2 * (size_t)j + 1]);
-            });
-        }
-    }
-    ncand[i] = n;
-    if (n > P.cap) atomicMax(overflow, n);
-    if (observed[i]) record_listers_serial(i, n, P.cap, out, taken0, lister);
+    if (point_window(A, i, W))
+        n = window_candidates_serial(cur.cell_off, cur.cell_idx, W.x0, W.x1, W.y0, W.y1, out, A.P.cap,
+                                     CandTest<Cur>{W, A.P.has_ur, cur});
+    A.ncand[i] = n;
+    if (n > A.P.cap) atomicMax(A.overflow, n);
+    if (A.observed[i]) record_listers(0, 1, i, n, A.P.cap, out, taken0(A), A.lister);
 }
-__global__ __launch_bounds__(kCandThreads) void k_lmp_candidates_t(const k_lmp_candidates_args A) {
-    k_lmp_candidates_t_body(blockIdx.x * kCandThreads + threadIdx.x, A.P, A.in_view, A.bad, A.proj, A.view_cos, A.depth, A.level, A.mp_desc, A.cur_kp, A.cur_ur,
-                            A.cur_desc, A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.taken0,
-                            A.lister);
+
+__global__ __launch_bounds__(64 * kCandWaves) void k_proj_candidates(const k_proj_candidates_args A) {
+    __shared__ int pre_s[kCandWaves][64], beg_s[kCandWaves][64];
+    candidates_wave(A, pre_s[threadIdx.x >> 6], beg_s[threadIdx.x >> 6]);
+}
+__global__ __launch_bounds__(64 * kCandWaves) void k_lmp_candidates(const k_lmp_candidates_args A) {
+    __shared__ int pre_s[kCandWaves][64], beg_s[kCandWaves][64];
+    candidates_wave(A, pre_s[threadIdx.x >> 6], beg_s[threadIdx.x >> 6]);
+}
+// a thread per point on frame blockIdx.y of a batch (one argument block per frame)
+__global__ __launch_bounds__(kCandThreads) void k_proj_candidates_t_b(const k_proj_candidates_args* __restrict__ a) {
+    const k_proj_candidates_args& A = a[blockIdx.y];
+    candidates_thread(A, blockIdx.x * kCandThreads + threadIdx.x, A.cur);
 }
 __global__ __launch_bounds__(kCandThreads) void k_lmp_candidates_t_b(const k_lmp_candidates_args* __restrict__ a) {
     const k_lmp_candidates_args& A = a[blockIdx.y];
-    k_lmp_candidates_t_body(blockIdx.x * kCandThreads + threadIdx.x, A.P, A.in_view, A.bad, A.proj, A.view_cos, A.depth, A.level, A.mp_desc, A.cur_kp, A.cur_ur,
-                            A.cur_desc, A.cell_off, A.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.taken0,
-                            A.lister);
+    candidates_thread(A, blockIdx.x * kCandThreads + threadIdx.x, A.cur);
 }
 
 // LDS-staged batch forms (round 6).  The thread forms above walk a window as a chain of dependent
@@ -505,36 +361,28 @@ __host__ __device__ constexpr size_t cand_lds_bytes(int cap) {
     return (size_t)cap * (32 + 16 + 4 + 4) + 4 * (size_t)(kGridCols * kGridRows + 1);
 }
 // (the staged records are read through orb_frame_grid.h's address-space-3 readers)
-struct CandLds {
-    LdsU4 desc;
-    LdsF4 kp;
-    LdsArr<float> ur;
-    LdsArr<int32_t> cell_idx;
-    LdsArr<int32_t> cell_off;
-};
+using CandLds = CurRecords<LdsF4, LdsArr<float>, LdsU4, LdsArr<int32_t>, LdsArr<int32_t>>;
 // descriptors | keypoint records | u_R | cell index list | cell offsets (16-B aligned sections); the
 // first `rows` keypoint rows are staged (the cell offsets always)
-__device__ __forceinline__ CandLds stage_frame_lds(uint8_t* smem, int cap, const float4* __restrict__ kp,
-                                                   const float* __restrict__ ur, const uint4* __restrict__ desc,
-                                                   const int32_t* __restrict__ cell_off, const int32_t* __restrict__ cell_idx,
-                                                   int rows) {
+__device__ __forceinline__ CandLds stage_frame_lds(uint8_t* smem, int cap, const CurRecords<>& g, int rows) {
     uint4* s_desc = reinterpret_cast<uint4*>(smem);
     float4* s_kp = reinterpret_cast<float4*>(smem + 32 * (size_t)cap);
     float* s_ur = reinterpret_cast<float*>(smem + 48 * (size_t)cap);
     int32_t* s_idx = reinterpret_cast<int32_t*>(smem + 52 * (size_t)cap);
     int32_t* s_off = reinterpret_cast<int32_t*>(smem + 56 * (size_t)cap);
     const int t = threadIdx.x;
-    for (int k = t; k < 2 * rows; k += kCandLdsThreads) s_desc[k] = desc[k];
+    for (int k = t; k < 2 * rows; k += kCandLdsThreads) s_desc[k] = g.desc[k];
     for (int k = t; k < rows; k += kCandLdsThreads) {
-        s_kp[k] = kp[k];
-        s_idx[k] = cell_idx[k];
-        if (ur) s_ur[k] = ur[k];
+        s_kp[k] = g.kp[k];
+        s_idx[k] = g.cell_idx[k];
+        if (g.ur) s_ur[k] = g.ur[k];
     }
-    for (int k = t; k <= kGridCols * kGridRows; k += kCandLdsThreads) s_off[k] = cell_off[k];
+    for (int k = t; k <= kGridCols * kGridRows; k += kCandLdsThreads) s_off[k] = g.cell_off[k];
     __syncthreads();
     // (u_R is read only when the frame has it, ProjParams / LocalParams has_ur)
-    return CandLds{LdsU4{(const ORB_LDS uint32_t*)s_desc}, LdsF4{(const ORB_LDS float*)s_kp}, LdsArr<float>{(const ORB_LDS float*)s_ur},
-                   LdsArr<int32_t>{(const ORB_LDS int32_t*)s_idx}, LdsArr<int32_t>{(const ORB_LDS int32_t*)s_off}};
+    return CandLds{LdsF4{(const ORB_LDS float*)s_kp}, LdsArr<float>{(const ORB_LDS float*)s_ur},
+                   LdsU4{(const ORB_LDS uint32_t*)s_desc}, LdsArr<int32_t>{(const ORB_LDS int32_t*)s_off},
+                   LdsArr<int32_t>{(const ORB_LDS int32_t*)s_idx}};
 }
 // ---- the in-order assignment, resolved by parallel fixed-point rounds ----------------------------
 // Both SearchByProjection loops visit the points in index order, and point i only sees the state the
@@ -717,12 +565,10 @@ __global__ __launch_bounds__(256) void k_resolve_init_b(const k_resolve_init_arg
 __global__ __launch_bounds__(kCandLdsThreads) void k_proj_candidates_l_b(const k_proj_candidates_args* __restrict__ a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t cand_smem[];
     const k_proj_candidates_args& A = a[blockIdx.x];
-    const int np = A.n_dev ? *A.n_dev : A.P.n_last;
+    const int np = n_points(A);
     if (np == 0) return;  // (a frame the motion gate turned off: nothing to stage)
-    const CandLds S = stage_frame_lds(cand_smem, A.P.cap, A.cur_kp, A.cur_ur, A.cur_desc, A.cell_off, A.cell_idx, A.P.cap);
-    for (int i = threadIdx.x; i < np; i += kCandLdsThreads)
-        k_proj_candidates_t_body(i, A.P, A.n_dev, A.valid, A.xyz, A.mp_desc, A.last_octave, S.kp, S.ur, S.desc, S.cell_off,
-                                 S.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.lister);
+    const CandLds S = stage_frame_lds(cand_smem, A.P.cap, A.cur, A.P.cap);
+    for (int i = threadIdx.x; i < np; i += kCandLdsThreads) candidates_thread(A, i, S);
 }
 __global__ __launch_bounds__(kCandLdsThreads) void k_lmp_candidates_l_b(const k_lmp_candidates_args* __restrict__ a,
                                                                         const k_resolve_init_args* __restrict__ ri) {
@@ -731,12 +577,8 @@ __global__ __launch_bounds__(kCandLdsThreads) void k_lmp_candidates_l_b(const k_
     const ResolveArgs& R = ri[blockIdx.x].a;
     if (A.P.n_pts == 0) return;
     // a frame without keypoints (the motion gate's failed frames) stages only its (empty) grid
-    const CandLds S = stage_frame_lds(cand_smem, A.P.cap, A.cur_kp, A.cur_ur, A.cur_desc, A.cell_off, A.cell_idx,
-                                      R.dims && R.dims[1] == 0 ? 0 : A.P.cap);
-    for (int i = threadIdx.x; i < A.P.n_pts; i += kCandLdsThreads)
-        k_lmp_candidates_t_body(i, A.P, A.in_view, A.bad, A.proj, A.view_cos, A.depth, A.level, A.mp_desc, S.kp, S.ur,
-                                S.desc, S.cell_off, S.cell_idx, A.cands, A.ncand, A.overflow, A.observed, A.taken0,
-                                A.lister);
+    const CandLds S = stage_frame_lds(cand_smem, A.P.cap, A.cur, R.dims && R.dims[1] == 0 ? 0 : A.P.cap);
+    for (int i = threadIdx.x; i < A.P.n_pts; i += kCandLdsThreads) candidates_thread(A, i, S);
 }
 
 // point i's answer in a round, from its kTop best (claims by earlier points excluded)
@@ -889,7 +731,7 @@ __device__ __forceinline__ void k_resolve_rounds_body(ResolveArgs a) {
         if (j < 0) continue;
         ++nsucc;
         atomicMax(&a.last[j], i);
-        if (a.check_ori) atomicAdd(&hist[rot_bin(a.last_angle[i], a.cur_kp[j].z)], 1);
+        if (a.check_ori) atomicAdd(&hist[orb_rot_bin(a.last_angle[i], a.cur_kp[j].z)], 1);
     }
     atomicAdd(&cnt[0], nsucc);
     __syncthreads();
@@ -900,7 +742,7 @@ __device__ __forceinline__ void k_resolve_rounds_body(ResolveArgs a) {
         for (int i = tid; i < a.n_pts; i += kResolveThreads) {
             const int j = a.st[i];
             if (j < 0) continue;
-            const int b = rot_bin(a.last_angle[i], a.cur_kp[j].z);
+            const int b = orb_rot_bin(a.last_angle[i], a.cur_kp[j].z);
             if (b != keep[0] && b != keep[1] && b != keep[2]) {
                 a.removed[j] = 1;
                 ++nrem;
@@ -930,17 +772,11 @@ __global__ __launch_bounds__(kResolveThreads) void k_resolve_rounds_b(const k_re
 }
 
 // ---- device-resident forms: the frame's grid and packed keypoints built on the device ------------
+// Each prep kernel takes its argument block by value; the _b form runs frame blockIdx.y of a batch
+// from one block per frame.
 
 // The grid build itself (k_frame_prep_body, with the scratch initialisation it does in place of fill
 // launches) is in orb_frame_grid.h, shared with Fuse.
-__global__ __launch_bounds__(kPrepThreads) void k_frame_prep(const orb_keypoint_t* __restrict__ kps,
-                                                             const int32_t* __restrict__ n_ptr, int cap, float min_x,
-                                                             float min_y, float inv_w, float inv_h,
-                                                             float4* __restrict__ kp4, int32_t* __restrict__ cell_off,
-                                                             int32_t* __restrict__ cell_idx, int32_t* __restrict__ cell_of,
-                                                             int32_t* n_out0, int32_t* n_out1, ScratchInit z) {
-    k_frame_prep_body(kps, n_ptr, cap, min_x, min_y, inv_w, inv_h, kp4, cell_off, cell_idx, cell_of, n_out0, n_out1, z);
-}
 struct k_frame_prep_args {
     const orb_keypoint_t* kps;
     const int32_t* n_ptr;
@@ -957,37 +793,17 @@ struct k_frame_prep_args {
     int32_t* n_out1;
     ScratchInit z;
 };
-// the same on frame blockIdx.y of a batch (one argument block per frame)
-__global__ __launch_bounds__(kPrepThreads) void k_frame_prep_b(const k_frame_prep_args* __restrict__ a) {
-    const k_frame_prep_args& A = a[blockIdx.y];
+__device__ __forceinline__ void frame_prep(const k_frame_prep_args& A) {
     k_frame_prep_body(A.kps, A.n_ptr, A.cap, A.min_x, A.min_y, A.inv_w, A.inv_h, A.kp4, A.cell_off, A.cell_idx,
                       A.cell_of, A.n_out0, A.n_out1, A.z);
+}
+__global__ __launch_bounds__(kPrepThreads) void k_frame_prep(const k_frame_prep_args A) { frame_prep(A); }
+__global__ __launch_bounds__(kPrepThreads) void k_frame_prep_b(const k_frame_prep_args* __restrict__ a) {
+    frame_prep(a[blockIdx.y]);
 }
 
 // the last frame's per-point inputs of k_proj_candidates / the rotation bins: a point whose octave is
 // outside the pyramid is not valid (the host form rejects the call instead)
-__device__ __forceinline__ void k_last_prep_body(const orb_keypoint_t* __restrict__ kps, const uint8_t* __restrict__ valid,
-                                                   const int32_t* __restrict__ n_ptr, int cap, int nlevels,
-                                                   uint8_t* __restrict__ valid2, int32_t* __restrict__ octave,
-                                                   float* __restrict__ angle, int32_t* n_out0, int32_t* n_out1) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(max(*n_ptr, 0), cap);
-    if (i == 0) {
-        *n_out0 = n;
-        if (n_out1) *n_out1 = n;
-    }
-    if (i >= n) return;
-    const orb_keypoint_t kp = kps[i];
-    octave[i] = kp.octave;
-    angle[i] = kp.angle;
-    valid2[i] = valid[i] && kp.octave >= 0 && kp.octave < nlevels;
-}
-__global__ __launch_bounds__(256) void k_last_prep(const orb_keypoint_t* __restrict__ kps, const uint8_t* __restrict__ valid,
-                                                   const int32_t* __restrict__ n_ptr, int cap, int nlevels,
-                                                   uint8_t* __restrict__ valid2, int32_t* __restrict__ octave,
-                                                   float* __restrict__ angle, int32_t* n_out0, int32_t* n_out1) {
-    k_last_prep_body(kps, valid, n_ptr, cap, nlevels, valid2, octave, angle, n_out0, n_out1);
-}
 struct k_last_prep_args {
     const orb_keypoint_t* kps;
     const uint8_t* valid;
@@ -1000,22 +816,23 @@ struct k_last_prep_args {
     int32_t* n_out0;
     int32_t* n_out1;
 };
-// the same on frame blockIdx.y of a batch (one argument block per frame)
-__global__ __launch_bounds__(256) void k_last_prep_b(const k_last_prep_args* __restrict__ a) {
-    const k_last_prep_args& A = a[blockIdx.y];
-    k_last_prep_body(A.kps, A.valid, A.n_ptr, A.cap, A.nlevels, A.valid2, A.octave, A.angle, A.n_out0, A.n_out1);
+__device__ __forceinline__ void last_prep(const k_last_prep_args& A) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(max(*A.n_ptr, 0), A.cap);
+    if (i == 0) {
+        *A.n_out0 = n;
+        if (A.n_out1) *A.n_out1 = n;
+    }
+    if (i >= n) return;
+    const orb_keypoint_t kp = A.kps[i];
+    A.octave[i] = kp.octave;
+    A.angle[i] = kp.angle;
+    A.valid2[i] = A.valid[i] && kp.octave >= 0 && kp.octave < A.nlevels;
 }
+__global__ __launch_bounds__(256) void k_last_prep(const k_last_prep_args A) { last_prep(A); }
+__global__ __launch_bounds__(256) void k_last_prep_b(const k_last_prep_args* __restrict__ a) { last_prep(a[blockIdx.y]); }
 
 // local map points: a predicted level outside the pyramid leaves the point out
-__device__ __forceinline__ void k_local_prep_body(const uint8_t* __restrict__ in_view, const int32_t* __restrict__ level,
-                                                    int n, int nlevels, uint8_t* __restrict__ in_view2) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) in_view2[i] = in_view[i] && level[i] >= 0 && level[i] < nlevels;
-}
-__global__ __launch_bounds__(256) void k_local_prep(const uint8_t* __restrict__ in_view, const int32_t* __restrict__ level,
-                                                    int n, int nlevels, uint8_t* __restrict__ in_view2) {
-    k_local_prep_body(in_view, level, n, nlevels, in_view2);
-}
 struct k_local_prep_args {
     const uint8_t* in_view;
     const int32_t* level;
@@ -1023,11 +840,14 @@ struct k_local_prep_args {
     int nlevels;
     uint8_t* in_view2;
 };
-// the same on frame blockIdx.y of a batch (one argument block per frame)
-__global__ __launch_bounds__(256) void k_local_prep_b(const k_local_prep_args* __restrict__ a) {
-    const k_local_prep_args& A = a[blockIdx.y];
-    k_local_prep_body(A.in_view, A.level, A.n, A.nlevels, A.in_view2);
+__device__ __forceinline__ void local_prep(const k_local_prep_args& A) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < A.n) A.in_view2[i] = A.in_view[i] && A.level[i] >= 0 && A.level[i] < A.nlevels;
 }
+__global__ __launch_bounds__(256) void k_local_prep(const k_local_prep_args A) { local_prep(A); }
+__global__ __launch_bounds__(256) void k_local_prep_b(const k_local_prep_args* __restrict__ a) { local_prep(a[blockIdx.y]); }
+
+// ---- host side ----------------------------------------------------------------------------------
 
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -1038,27 +858,14 @@ bool resolve_lds_ready() {
     return ok;
 }
 
-// Device forms' candidate pass: one wave per point or one thread per point; both write the same lists.
-// A single frame's few thousand points leave the chip mostly idle, and a wave's parallel window scan
-// has the shorter latency (0.51 vs 0.65 ms per tracked frame); a batch fills the chip, and threads
-// carry far less per-point machinery (256 frames: 3.2 -> 1.5 ms per call).  ORBGPU_CAND_MODE=wave /
-// thread forces one form everywhere (A/B).
-int cand_forced_mode() {
-    static const int forced = [] {
-        const char* c = getenv("ORBGPU_CAND_MODE");
-        return !c ? -1 : strcmp(c, "lds") == 0 ? 2 : strcmp(c, "thread") == 0 ? 1 : strcmp(c, "wave") == 0 ? 0 : -1;
-    }();
-    return forced;
-}
-bool cand_thread_mode(bool batch) {
-    const int forced = cand_forced_mode();
-    return forced >= 0 ? forced >= 1 : batch;
-}
-// A batch's candidate pass in the LDS-staged form (k_*_candidates_l_b) unless a form is forced
-// (ORBGPU_CAND_MODE=thread / wave) or the frame's records do not fit one workgroup's LDS.
+// The candidate pass is one wave per point for a single call and one thread per point for a batch;
+// both write the same lists.  A single frame's few thousand points leave the chip mostly idle, and a
+// wave's parallel window scan has the shorter latency (0.51 vs 0.65 ms per tracked frame); a batch
+// fills the chip, and threads carry far less per-point machinery (256 frames: 3.2 -> 1.5 ms per call).
+// A batch takes the LDS-staged form (k_*_candidates_l_b) unless the frame's records do not fit one
+// workgroup's LDS; then the threads read global memory (k_*_candidates_t_b).
 bool cand_lds_mode(int cap) {
-    const int forced = cand_forced_mode();
-    if (!(forced == -1 || forced == 2) || cap > kCandLdsCap) return false;
+    if (cap > kCandLdsCap) return false;
     static const bool ready = [] {
         return hipFuncSetAttribute((const void*)k_proj_candidates_l_b, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)cand_lds_bytes(kCandLdsCap)) == hipSuccess &&
@@ -1068,13 +875,237 @@ bool cand_lds_mode(int cap) {
     return ready;
 }
 
-}  // namespace
+int sbp_fail(int code, const char* before, const char* name, const char* after) {
+    return orbgpu_fail(code, (std::string(before) + name + after).c_str());
+}
 
-// Defined in orb_triangulation.hip: the matcher handle's staging buffers and ratio.
-int orbgpu_matcher_reserve(orb_matcher_t m, size_t bytes, char** d_buf, char** h_buf, hipStream_t* stream,
-                           int* check_ori);
-float orbgpu_matcher_nnratio(orb_matcher_t m);
-int orbgpu_matcher_check_ori(orb_matcher_t m);
+// A call's scratch, carved in 256-B aligned pieces.  A layout is run once with a null base for its
+// size (z.off) and once with the real base for the pointers, so the two cannot disagree.
+struct DevScratch {
+    char* base = nullptr;
+    size_t off = 0;
+    template <class T>
+    T* take(size_t count) {
+        T* p = reinterpret_cast<T*>(base + off);
+        off = align256(off + std::max<size_t>(count, 1) * sizeof(T));
+        return p;
+    }
+};
+
+// Frame is orb_frame_view_t or orb_frame_device_t: the same scalar fields.
+template <class Frame>
+ProjParams make_proj_params(const Frame* cur, const float* last_Tcw, float th, int mono, int n_cur, int n_last, int cap,
+                            int check_ori) {
+    ProjParams P{};
+    memcpy(P.Tcw, cur->Tcw, sizeof(P.Tcw));
+    P.min_x = cur->min_x; P.max_x = cur->max_x; P.min_y = cur->min_y; P.max_y = cur->max_y;
+    P.inv_w = cur->grid_inv_w; P.inv_h = cur->grid_inv_h;
+    P.fx = cur->fx; P.fy = cur->fy; P.cx = cur->cx; P.cy = cur->cy; P.bf = cur->bf; P.th = th;
+    for (int l = 0; l < cur->nlevels; ++l) P.scale[l] = cur->scale_factors[l];
+    P.n_cur = n_cur; P.n_last = n_last; P.has_ur = cur->u_right != nullptr;
+    {   // twc = -R^T t, tlc = Tlw * twc (src:1960-1968)
+        const float* T = cur->Tcw;
+        float twc[3], tlc[3];
+        for (int i = 0; i < 3; ++i) twc[i] = -std::fma(T[8 + i], T[11], std::fma(T[i], T[3], T[4 + i] * T[7]));
+        for (int i = 0; i < 3; ++i)
+            tlc[i] = std::fma(last_Tcw[4 * i + 2], twc[2], std::fma(last_Tcw[4 * i], twc[0], last_Tcw[4 * i + 1] * twc[1])) +
+                     last_Tcw[4 * i + 3];
+        P.bForward = tlc[2] > cur->b && !mono;
+        P.bBackward = -tlc[2] > cur->b && !mono;
+    }
+    P.cap = cap;
+    P.check_ori = check_ori;
+    return P;
+}
+
+template <class Frame>
+LocalParams make_local_params(const Frame* F, float th, int far_points, float th_far_points, int n_cur, int n_pts,
+                              int cap, float nnratio) {
+    LocalParams P{};
+    P.min_x = F->min_x; P.min_y = F->min_y; P.inv_w = F->grid_inv_w; P.inv_h = F->grid_inv_h;
+    P.th = th; P.th_far = th_far_points; P.nnratio = nnratio;
+    for (int l = 0; l < F->nlevels; ++l) P.scale[l] = F->scale_factors[l];
+    P.n_cur = n_cur; P.n_pts = n_pts; P.has_ur = F->u_right != nullptr; P.far = far_points ? 1 : 0; P.nlevels = F->nlevels;
+    P.cap = cap;
+    return P;
+}
+
+// The candidate lists and the resolver's working set of one call, n_cur keypoints and np points:
+// lister + fixed claims (to be initialised 0x7f..) | overflow word + 3 counters (0) | host forms: the
+// match array, downloaded with the counters | candidates | ncand | st | claimMin, last, removed |
+// work list | kTop best | usable counts
+struct ResolveScratch {
+    int32_t* lf;
+    int32_t* ovf;
+    int32_t* mp;
+    Cand* cands;
+    int32_t* ncand;
+    int32_t* st;
+    int32_t* kw;
+    int32_t* work;
+    int4* top;
+    int32_t* nusable;
+};
+ResolveScratch carve_resolve(DevScratch& z, int n_cur, int np, int cap, bool host_match) {
+    ResolveScratch r;
+    r.lf = z.take<int32_t>(2 * (size_t)n_cur);
+    r.ovf = z.take<int32_t>(4);
+    r.mp = host_match ? z.take<int32_t>(n_cur) : nullptr;
+    r.cands = z.take<Cand>((size_t)np * cap);
+    r.ncand = z.take<int32_t>(np);
+    r.st = z.take<int32_t>(np);
+    r.kw = z.take<int32_t>(3 * (size_t)n_cur);
+    r.work = z.take<int32_t>(np);
+    r.top = z.take<int4>((kTop / 2) * (size_t)np);
+    r.nusable = z.take<int32_t>(np);
+    return r;
+}
+
+// The resolver's arguments over a ResolveScratch.  Host forms: n_pts / n_cur are the counts, the
+// matches go to r.mp; device forms: they are the capacities, the counts come from `dims` on the device,
+// and the matches and the count go to the caller's mp / out_user.
+ResolveArgs make_resolve_args(const ResolveScratch& r, int n_pts, int n_cur, int cap, int local, int check_ori,
+                              float nnratio, const uint8_t* observed, const uint8_t* taken0, const float4* cur_kp,
+                              const float* last_angle, int32_t* mp, const int32_t* dims, int32_t* out_user) {
+    const size_t nk = (size_t)std::max(n_cur, 1);  // (a piece of the scratch is never empty)
+    ResolveArgs ra{};
+    ra.n_pts = n_pts; ra.n_cur = n_cur; ra.cap = cap; ra.local = local; ra.check_ori = check_ori; ra.nnratio = nnratio;
+    ra.cands = r.cands; ra.ncand = r.ncand; ra.observed = observed; ra.taken0 = taken0; ra.cur_kp = cur_kp;
+    ra.last_angle = last_angle; ra.overflow = r.ovf; ra.st = r.st;
+    ra.claimMin = r.kw; ra.last = r.kw + nk; ra.removed = r.kw + 2 * nk;
+    ra.lister = r.lf; ra.fixed = r.lf + nk; ra.work = r.work; ra.top = r.top; ra.nusable = r.nusable;
+    ra.lds_keypoints = n_cur <= kResolveLdsKeypoints && resolve_lds_ready() ? 1 : 0;
+    ra.mp = mp; ra.out_n = r.ovf + 1; ra.dims = dims; ra.out_user = out_user;
+    return ra;
+}
+
+// ---- host forms: one upload (inputs, initialised words), the kernels, one download ---------------
+
+// Frame::AssignFeaturesToGrid: cell (round((x - mnMinX) * inv_w), round((y - mnMinY) * inv_h)),
+// keypoints in index order inside each cell
+void assign_features_to_grid(const orb_frame_view_t* F, std::vector<int32_t>& cell_off, std::vector<int32_t>& cell_idx) {
+    const int n = F->n;
+    cell_off.assign(kCells + 1, 0);
+    std::vector<int32_t> cell_of(n, -1);
+    for (int i = 0; i < n; ++i) {
+        const orb_keypoint_t& kp = F->kps_un[i];
+        const int px = (int)std::round((kp.x - F->min_x) * F->grid_inv_w);
+        const int py = (int)std::round((kp.y - F->min_y) * F->grid_inv_h);
+        if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) continue;
+        cell_of[i] = px * kGridRows + py;
+        cell_off[cell_of[i] + 1]++;
+    }
+    for (int c = 0; c < kCells; ++c) cell_off[c + 1] += cell_off[c];
+    cell_idx.resize(cell_off.back());
+    std::vector<int32_t> fill(cell_off.begin(), cell_off.end() - 1);
+    for (int i = 0; i < n; ++i)
+        if (cell_of[i] >= 0) cell_idx[fill[cell_of[i]]++] = i;
+}
+
+// the (x, y, angle, octave bits) rows the kernels read
+void pack_kp4(const orb_frame_view_t* F, float4* kp4) {
+    for (int i = 0; i < F->n; ++i) {
+        const orb_keypoint_t& kp = F->kps_un[i];
+        kp4[i].x = kp.x;
+        kp4[i].y = kp.y;
+        kp4[i].z = kp.angle;
+        memcpy(&kp4[i].w, &kp.octave, 4);
+    }
+}
+
+// One attempt of a host call.  The pinned block h and the device block d share one layout: the
+// current frame | the overload's points | ResolveScratch; everything before r.mp goes up in one copy,
+// the overflow block and the matches come back in one.
+struct HostCall {
+    char* d = nullptr;
+    char* h = nullptr;
+    hipStream_t s = nullptr;
+    int check_ori = 0, cap = 0;
+    float4* kp4;
+    float* ur;
+    uint4* desc;
+    uint8_t* taken;  // NULL: the call has none
+    int32_t* cell_off;
+    int32_t* cell_idx;
+    ResolveScratch r;
+    // the host mirror of a device piece
+    template <class T>
+    T* host(T* p) const { return reinterpret_cast<T*>(h + (reinterpret_cast<char*>(p) - d)); }
+    // ... filled from a caller's array of n elements
+    template <class T, class S>
+    void put(T* p, const S* src, size_t n) const { if (n) memcpy(host(p), src, n * sizeof(S)); }
+    CurRecords<> cur() const { return CurRecords<>{kp4, ur, desc, cell_off, cell_idx}; }
+};
+
+// A host SearchByProjection: the grid, then up to three attempts (a point with more candidates than
+// the capacity makes the resolve a no-op, and the call is redone with room for all).  layout(z) carves
+// the overload's point arrays; stage(call, cand_args) fills their host mirrors, sets the candidate
+// kernel's arguments and returns the resolver's.
+template <class CandArgs, class Layout, class Stage>
+int host_search(orb_matcher_t m, const orb_frame_view_t* F, const uint8_t* frame_taken, int np, int32_t* match,
+                int32_t* n_matches, const char* name, void (*cand_kernel)(const CandArgs), Layout layout, Stage stage) {
+    const int n = F->n;
+    std::vector<int32_t> cell_off, cell_idx;
+    assign_features_to_grid(F, cell_off, cell_idx);
+    HostCall c;
+    c.cap = 128;
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        const auto carve = [&](char* base) {
+            DevScratch z;
+            z.base = base;
+            c.kp4 = z.take<float4>(n);
+            c.ur = z.take<float>(n);
+            c.desc = z.take<uint4>(2 * (size_t)n);
+            c.taken = frame_taken ? z.take<uint8_t>(n) : nullptr;
+            c.cell_off = z.take<int32_t>(cell_off.size());
+            c.cell_idx = z.take<int32_t>(cell_idx.size());
+            layout(z);
+            c.r = carve_resolve(z, n, np, c.cap, true);
+            return z.off;
+        };
+        if (int rc = orbgpu_matcher_reserve(m, carve(nullptr), &c.d, &c.h, &c.s, &c.check_ori)) return rc;
+        carve(c.d);
+        pack_kp4(F, c.host(c.kp4));
+        if (F->u_right) c.put(c.ur, F->u_right, n);
+        c.put(c.desc, F->desc, (size_t)n * 32);
+        if (frame_taken) c.put(c.taken, frame_taken, n);
+        c.put(c.cell_off, cell_off.data(), cell_off.size());
+        c.put(c.cell_idx, cell_idx.data(), cell_idx.size());
+        // initialised with the inputs (no fills): the lister / fixed claims (0x7f..) and the overflow
+        // word + counters (0), which the one download then reads back with the matches
+        const size_t nk = (size_t)std::max(n, 1);
+        memset(c.host(c.r.lf), 0x7f, nk * 8);
+        memset(c.host(c.r.ovf), 0, 16);
+        CandArgs ca;
+        const ResolveArgs ra = stage(c, ca);
+        bool ok = hipMemcpyAsync(c.d, c.h, reinterpret_cast<char*>(c.r.mp) - c.d, hipMemcpyHostToDevice, c.s) == hipSuccess;
+        // candidates and the rounds back to back, one synchronisation
+        if (ok) {
+            if (np > 0) {
+                hipLaunchKernelGGL(cand_kernel, dim3((np + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, c.s, ca);
+                hipLaunchKernelGGL(k_resolve_init, dim3((np + 255) / 256), dim3(256), 0, c.s, ra);
+            }
+            hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), ra.lds_keypoints ? 8 * (size_t)n : 0, c.s,
+                               ra);
+        }
+        const size_t back = reinterpret_cast<char*>(c.r.mp + nk) - reinterpret_cast<char*>(c.r.ovf);
+        ok = ok && hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(c.host(c.r.ovf), c.r.ovf, back, hipMemcpyDeviceToHost, c.s) == hipSuccess &&
+             hipStreamSynchronize(c.s) == hipSuccess;
+        if (!ok) return sbp_fail(ORB_ERR_DEVICE, "", name, " failed");
+        const int32_t ovf = c.host(c.r.ovf)[0];
+        if (ovf > c.cap) {
+            c.cap = (ovf + 63) & ~63;
+            continue;
+        }
+        if (n) memcpy(match, c.host(c.r.mp), (size_t)n * 4);
+        *n_matches = c.host(c.r.ovf)[1];
+        return ORB_OK;
+    }
+    return sbp_fail(ORB_ERR_INTERNAL, "", name, " candidate capacity");
+}
+
+}  // namespace
 
 extern "C" int orb_search_by_projection_frame(orb_matcher_t m, const orb_frame_view_t* cur, const orb_last_points_t* last,
                                               float th, int mono, int32_t* match, int32_t* n_matches) {
@@ -1086,149 +1117,36 @@ extern "C" int orb_search_by_projection_frame(orb_matcher_t m, const orb_frame_v
     for (int i = 0; i < last->n; ++i)
         if (last->valid[i] && (last->kps_un[i].octave < 0 || last->kps_un[i].octave >= cur->nlevels))
             return orbgpu_fail(ORB_ERR_ARG, "last-frame octave out of range");
-    const int n = cur->n, nl = last->n;
-    // Frame::AssignFeaturesToGrid: cell (round((x - mnMinX) * inv_w), round((y - mnMinY) * inv_h)),
-    // keypoints in index order inside each cell
-    std::vector<int32_t> cell_off(kGridCols * kGridRows + 1, 0), cell_idx;
-    std::vector<int32_t> cell_of(n, -1);
-    for (int i = 0; i < n; ++i) {
-        const orb_keypoint_t& kp = cur->kps_un[i];
-        const int px = (int)std::round((kp.x - cur->min_x) * cur->grid_inv_w);
-        const int py = (int)std::round((kp.y - cur->min_y) * cur->grid_inv_h);
-        if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) continue;
-        cell_of[i] = px * kGridRows + py;
-        cell_off[cell_of[i] + 1]++;
-    }
-    for (int c = 0; c < kGridCols * kGridRows; ++c) cell_off[c + 1] += cell_off[c];
-    cell_idx.resize(cell_off.back());
-    {
-        std::vector<int32_t> fill(cell_off.begin(), cell_off.end() - 1);
-        for (int i = 0; i < n; ++i)
-            if (cell_of[i] >= 0) cell_idx[fill[cell_of[i]]++] = i;
-    }
-    ProjParams P{};
-    memcpy(P.Tcw, cur->Tcw, sizeof(P.Tcw));
-    P.min_x = cur->min_x; P.max_x = cur->max_x; P.min_y = cur->min_y; P.max_y = cur->max_y;
-    P.inv_w = cur->grid_inv_w; P.inv_h = cur->grid_inv_h;
-    P.fx = cur->fx; P.fy = cur->fy; P.cx = cur->cx; P.cy = cur->cy; P.bf = cur->bf; P.th = th;
-    for (int l = 0; l < cur->nlevels; ++l) P.scale[l] = cur->scale_factors[l];
-    P.n_cur = n; P.n_last = nl; P.has_ur = cur->u_right != nullptr;
-    {   // twc = -R^T t, tlc = Tlw * twc (src:1960-1968)
-        const float* T = cur->Tcw;
-        float twc[3], tlc[3];
-        for (int i = 0; i < 3; ++i) twc[i] = -std::fma(T[8 + i], T[11], std::fma(T[i], T[3], T[4 + i] * T[7]));
-        for (int i = 0; i < 3; ++i)
-            tlc[i] = std::fma(last->Tcw[4 * i + 2], twc[2], std::fma(last->Tcw[4 * i], twc[0], last->Tcw[4 * i + 1] * twc[1])) +
-                     last->Tcw[4 * i + 3];
-        P.bForward = tlc[2] > cur->b && !mono;
-        P.bBackward = -tlc[2] > cur->b && !mono;
-    }
-    P.cap = 128;
-    // packed inputs: params | cur kp (float4) | cur ur | cur desc | cells | last valid | observed | xyz |
-    // mp desc | last octave | last angle | outputs (cands, ncand, best_c, overflow, mp, match lists, n)
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        char* d = nullptr;
-        char* h = nullptr;
-        hipStream_t s = nullptr;
-        int check_ori = 0;
-        size_t off = 0;
-        const size_t o_p = off; off = align256(off + sizeof(ProjParams));
-        const size_t o_kp = off; off = align256(off + (size_t)n * 16);
-        const size_t o_ur = off; off = align256(off + (size_t)n * 4);
-        const size_t o_cd = off; off = align256(off + (size_t)n * 32);
-        const size_t o_co = off; off = align256(off + cell_off.size() * 4);
-        const size_t o_ci = off; off = align256(off + cell_idx.size() * 4);
-        const size_t o_va = off; off = align256(off + (size_t)nl);
-        const size_t o_ob = off; off = align256(off + (size_t)nl);
-        const size_t o_xyz = off; off = align256(off + (size_t)nl * 12);
-        const size_t o_md = off; off = align256(off + (size_t)nl * 32);
-        const size_t o_lo = off; off = align256(off + (size_t)nl * 4);
-        const size_t o_la = off; off = align256(off + (size_t)nl * 4);
-        // initialised with the inputs (one upload, no fills): the lister / fixed claims (0x7f..) and
-        // the overflow word + counters (0), which the one download then reads back with the matches
-        const size_t o_lf = off; off = align256(off + (size_t)std::max(n, 1) * 8);
-        const size_t o_ovf = off; off = align256(off + 16);
-        const size_t in_bytes = off;
-        const size_t o_mp = off; off = align256(off + (size_t)std::max(n, 1) * 4);
-        const size_t o_cand = off; off = align256(off + (size_t)nl * P.cap * sizeof(Cand));
-        const size_t o_nc = off; off = align256(off + (size_t)nl * 4);
-        const size_t o_st = off; off = align256(off + (size_t)std::max(nl, 1) * 4);
-        const size_t o_kw = off; off = align256(off + (size_t)std::max(n, 1) * 12);  // claimMin, last, removed
-        const size_t o_wl = off; off = align256(off + (size_t)std::max(nl, 1) * 4);  // resolve work list
-        const size_t o_top = off; off = align256(off + (size_t)std::max(nl, 1) * 68);  // 8 best (64 B) + usable count
-        if (int rc = orbgpu_matcher_reserve(m, off, &d, &h, &s, &check_ori)) return rc;
-        P.check_ori = check_ori;
-        memcpy(h + o_p, &P, sizeof(P));
-        float* kp4 = reinterpret_cast<float*>(h + o_kp);
-        for (int i = 0; i < n; ++i) {
-            kp4[4 * i] = cur->kps_un[i].x;
-            kp4[4 * i + 1] = cur->kps_un[i].y;
-            kp4[4 * i + 2] = cur->kps_un[i].angle;
-            memcpy(&kp4[4 * i + 3], &cur->kps_un[i].octave, 4);
-        }
-        if (cur->u_right) memcpy(h + o_ur, cur->u_right, (size_t)n * 4);
-        if (n) memcpy(h + o_cd, cur->desc, (size_t)n * 32);
-        memcpy(h + o_co, cell_off.data(), cell_off.size() * 4);
-        if (!cell_idx.empty()) memcpy(h + o_ci, cell_idx.data(), cell_idx.size() * 4);
-        if (nl) {
-            memcpy(h + o_va, last->valid, nl);
-            memcpy(h + o_ob, last->observed, nl);
-            memcpy(h + o_xyz, last->xyz, (size_t)nl * 12);
-            memcpy(h + o_md, last->desc, (size_t)nl * 32);
-        }
-        int32_t* lo = reinterpret_cast<int32_t*>(h + o_lo);
-        float* la = reinterpret_cast<float*>(h + o_la);
-        for (int i = 0; i < nl; ++i) {
-            lo[i] = last->kps_un[i].octave;
-            la[i] = last->kps_un[i].angle;
-        }
-        memset(h + o_lf, 0x7f, (size_t)std::max(n, 1) * 8);
-        memset(h + o_ovf, 0, 16);
-        bool ok = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-        if (ok && nl > 0)
-            hipLaunchKernelGGL(k_proj_candidates, dim3((nl + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, s, P,
-                               (const int32_t*)nullptr,
-                               (const uint8_t*)(d + o_va), (const float*)(d + o_xyz), (const uint4*)(d + o_md),
-                               (const int32_t*)(d + o_lo), (const float4*)(d + o_kp), (const float*)(d + o_ur),
-                               (const uint4*)(d + o_cd), (const int32_t*)(d + o_co), (const int32_t*)(d + o_ci),
-                               (Cand*)(d + o_cand), (int32_t*)(d + o_nc), (int32_t*)(d + o_ovf), (const uint8_t*)(d + o_ob),
-                               (int32_t*)(d + o_lf));
-        ResolveArgs ra{};
-        ra.n_pts = nl; ra.n_cur = n; ra.cap = P.cap; ra.local = 0; ra.check_ori = check_ori; ra.nnratio = 0.f;
-        ra.cands = (const Cand*)(d + o_cand); ra.ncand = (const int32_t*)(d + o_nc); ra.observed = (const uint8_t*)(d + o_ob);
-        ra.taken0 = nullptr; ra.cur_kp = (const float4*)(d + o_kp); ra.last_angle = (const float*)(d + o_la);
-        ra.overflow = (const int32_t*)(d + o_ovf); ra.st = (int32_t*)(d + o_st);
-        int32_t* kw = (int32_t*)(d + o_kw);
-        const size_t nk = (size_t)std::max(n, 1);
-        ra.claimMin = kw; ra.last = kw + nk; ra.removed = kw + 2 * nk;
-        ra.lister = (int32_t*)(d + o_lf); ra.fixed = (int32_t*)(d + o_lf) + nk;
-        ra.work = (int32_t*)(d + o_wl);
-        ra.top = (int4*)(d + o_top); ra.nusable = (int32_t*)(d + o_top + (size_t)std::max(nl, 1) * 64);
-        ra.lds_keypoints = n <= kResolveLdsKeypoints && resolve_lds_ready() ? 1 : 0;
-        ra.mp = (int32_t*)(d + o_mp); ra.out_n = (int32_t*)(d + o_ovf) + 1;
-        // candidates and the rounds back to back, one synchronisation; an overflowing candidate pass
-        // (a point with more candidates than the capacity) makes the resolve a no-op and is re-run
-        if (ok) {
-            if (ra.n_pts > 0) hipLaunchKernelGGL(k_resolve_init, dim3((ra.n_pts + 255) / 256), dim3(256), 0, s, ra);
-            hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), ra.lds_keypoints ? 8 * (size_t)n : 0,
-                               s, ra);
-        }
-        ok = ok && hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(h + o_ovf, d + o_ovf, o_mp - o_ovf + (size_t)std::max(n, 1) * 4, hipMemcpyDeviceToHost, s) ==
-                 hipSuccess &&
-             hipStreamSynchronize(s) == hipSuccess;
-        if (!ok) return orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection failed");
-        int32_t ovf = 0;
-        memcpy(&ovf, h + o_ovf, 4);
-        if (ovf > P.cap) {  // a point had more candidates than the capacity: redo with room for all
-            P.cap = (ovf + 63) & ~63;
-            continue;
-        }
-        if (n) memcpy(match, h + o_mp, (size_t)n * 4);
-        memcpy(n_matches, h + o_ovf + 4, 4);
-        return ORB_OK;
-    }
-    return orbgpu_fail(ORB_ERR_INTERNAL, "SearchByProjection candidate capacity");
+    const int nl = last->n;
+    uint8_t *valid, *observed;
+    float *xyz, *angle;
+    uint4* desc;
+    int32_t* octave;
+    return host_search<k_proj_candidates_args>(
+        m, cur, nullptr, nl, match, n_matches, "SearchByProjection", k_proj_candidates,
+        [&](DevScratch& z) {
+            valid = z.take<uint8_t>(nl);
+            observed = z.take<uint8_t>(nl);
+            xyz = z.take<float>(3 * (size_t)nl);
+            desc = z.take<uint4>(2 * (size_t)nl);
+            octave = z.take<int32_t>(nl);
+            angle = z.take<float>(nl);
+        },
+        [&](const HostCall& c, k_proj_candidates_args& ca) {
+            c.put(valid, last->valid, nl);
+            c.put(observed, last->observed, nl);
+            c.put(xyz, last->xyz, 3 * (size_t)nl);
+            c.put(desc, last->desc, (size_t)nl * 32);
+            for (int i = 0; i < nl; ++i) {
+                c.host(octave)[i] = last->kps_un[i].octave;
+                c.host(angle)[i] = last->kps_un[i].angle;
+            }
+            const ProjParams P = make_proj_params(cur, last->Tcw, th, mono, cur->n, nl, c.cap, c.check_ori);
+            ca = k_proj_candidates_args{P, nullptr, valid, xyz, desc, octave, c.cur(), c.r.cands, c.r.ncand, c.r.ovf,
+                                        observed, c.r.lf};
+            return make_resolve_args(c.r, nl, cur->n, c.cap, 0, c.check_ori, 0.f, observed, nullptr, c.kp4, angle, c.r.mp,
+                                     nullptr, nullptr);
+        });
 }
 
 extern "C" int orb_search_by_projection_local(orb_matcher_t m, const orb_frame_view_t* F, const uint8_t* frame_taken,
@@ -1243,143 +1161,44 @@ extern "C" int orb_search_by_projection_local(orb_matcher_t m, const orb_frame_v
     for (int i = 0; i < pts->n; ++i)
         if (pts->track_in_view[i] && (pts->track_level[i] < 0 || pts->track_level[i] >= F->nlevels))
             return orbgpu_fail(ORB_ERR_ARG, "predicted level out of range");
-    const int n = F->n, np = pts->n;
-    std::vector<int32_t> cell_off(kGridCols * kGridRows + 1, 0), cell_idx, cell_of(n, -1);
-    for (int i = 0; i < n; ++i) {  // Frame::AssignFeaturesToGrid
-        const int px = (int)std::round((F->kps_un[i].x - F->min_x) * F->grid_inv_w);
-        const int py = (int)std::round((F->kps_un[i].y - F->min_y) * F->grid_inv_h);
-        if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) continue;
-        cell_of[i] = px * kGridRows + py;
-        cell_off[cell_of[i] + 1]++;
-    }
-    for (int c = 0; c < kGridCols * kGridRows; ++c) cell_off[c + 1] += cell_off[c];
-    cell_idx.resize(cell_off.back());
-    {
-        std::vector<int32_t> fill(cell_off.begin(), cell_off.end() - 1);
-        for (int i = 0; i < n; ++i)
-            if (cell_of[i] >= 0) cell_idx[fill[cell_of[i]]++] = i;
-    }
-    LocalParams P{};
-    P.min_x = F->min_x; P.min_y = F->min_y; P.inv_w = F->grid_inv_w; P.inv_h = F->grid_inv_h;
-    P.th = th; P.th_far = th_far_points;
-    for (int l = 0; l < F->nlevels; ++l) P.scale[l] = F->scale_factors[l];
-    P.n_cur = n; P.n_pts = np; P.has_ur = F->u_right != nullptr; P.far = far_points ? 1 : 0; P.nlevels = F->nlevels;
-    P.cap = 128;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        char *d = nullptr, *h = nullptr;
-        hipStream_t s = nullptr;
-        int check_ori = 0;
-        size_t off = 0;
-        const size_t o_p = off; off = align256(off + sizeof(LocalParams));
-        const size_t o_kp = off; off = align256(off + (size_t)n * 16);
-        const size_t o_ur = off; off = align256(off + (size_t)n * 4);
-        const size_t o_cd = off; off = align256(off + (size_t)n * 32);
-        const size_t o_tk = off; off = align256(off + (size_t)n);
-        const size_t o_co = off; off = align256(off + cell_off.size() * 4);
-        const size_t o_ci = off; off = align256(off + cell_idx.size() * 4);
-        const size_t o_iv = off; off = align256(off + (size_t)np);
-        const size_t o_bd = off; off = align256(off + (size_t)np);
-        const size_t o_ob = off; off = align256(off + (size_t)np);
-        const size_t o_pj = off; off = align256(off + (size_t)np * 12);
-        const size_t o_vc = off; off = align256(off + (size_t)np * 4);
-        const size_t o_dp = off; off = align256(off + (size_t)np * 4);
-        const size_t o_lv = off; off = align256(off + (size_t)np * 4);
-        const size_t o_md = off; off = align256(off + (size_t)np * 32);
-        const size_t o_lf = off; off = align256(off + (size_t)std::max(n, 1) * 8);  // lister, fixed (0x7f..)
-        const size_t o_ovf = off; off = align256(off + 16);                          // overflow + counters (0)
-        const size_t in_bytes = off;
-        const size_t o_m = off; off = align256(off + (size_t)std::max(n, 1) * 4);
-        const size_t o_cand = off; off = align256(off + (size_t)np * P.cap * sizeof(Cand));
-        const size_t o_nc = off; off = align256(off + (size_t)np * 4);
-        const size_t o_st = off; off = align256(off + (size_t)std::max(np, 1) * 4);
-        const size_t o_kw = off; off = align256(off + (size_t)std::max(n, 1) * 12);  // claimMin, last, removed
-        const size_t o_wl = off; off = align256(off + (size_t)std::max(np, 1) * 4);  // resolve work list
-        const size_t o_top = off; off = align256(off + (size_t)std::max(np, 1) * 68);  // 8 best (64 B) + usable count
-        if (int rc = orbgpu_matcher_reserve(m, off, &d, &h, &s, &check_ori)) return rc;
-        P.nnratio = orbgpu_matcher_nnratio(m);
-        memcpy(h + o_p, &P, sizeof(P));
-        float* kp4 = reinterpret_cast<float*>(h + o_kp);
-        for (int i = 0; i < n; ++i) {
-            kp4[4 * i] = F->kps_un[i].x;
-            kp4[4 * i + 1] = F->kps_un[i].y;
-            kp4[4 * i + 2] = F->kps_un[i].angle;
-            memcpy(&kp4[4 * i + 3], &F->kps_un[i].octave, 4);
-        }
-        if (F->u_right) memcpy(h + o_ur, F->u_right, (size_t)n * 4);
-        if (n) memcpy(h + o_cd, F->desc, (size_t)n * 32);
-        if (frame_taken && n) memcpy(h + o_tk, frame_taken, n);
-        memcpy(h + o_co, cell_off.data(), cell_off.size() * 4);
-        if (!cell_idx.empty()) memcpy(h + o_ci, cell_idx.data(), cell_idx.size() * 4);
-        if (np) {
-            memcpy(h + o_iv, pts->track_in_view, np);
-            memcpy(h + o_bd, pts->is_bad, np);
-            memcpy(h + o_ob, pts->observed, np);
-            memcpy(h + o_pj, pts->track_proj, (size_t)np * 12);
-            memcpy(h + o_vc, pts->track_view_cos, (size_t)np * 4);
-            memcpy(h + o_dp, pts->track_depth, (size_t)np * 4);
-            memcpy(h + o_lv, pts->track_level, (size_t)np * 4);
-            memcpy(h + o_md, pts->desc, (size_t)np * 32);
-        }
-        memset(h + o_lf, 0x7f, (size_t)std::max(n, 1) * 8);
-        memset(h + o_ovf, 0, 16);
-        bool ok = hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-        if (ok && np > 0)
-            hipLaunchKernelGGL(k_lmp_candidates, dim3((np + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, s, P,
-                               (const uint8_t*)(d + o_iv), (const uint8_t*)(d + o_bd), (const float*)(d + o_pj),
-                               (const float*)(d + o_vc), (const float*)(d + o_dp), (const int32_t*)(d + o_lv),
-                               (const uint4*)(d + o_md), (const float4*)(d + o_kp), (const float*)(d + o_ur),
-                               (const uint4*)(d + o_cd), (const int32_t*)(d + o_co), (const int32_t*)(d + o_ci),
-                               (Cand*)(d + o_cand), (int32_t*)(d + o_nc), (int32_t*)(d + o_ovf), (const uint8_t*)(d + o_ob),
-                               frame_taken ? (const uint8_t*)(d + o_tk) : nullptr, (int32_t*)(d + o_lf));
-        ResolveArgs ra{};
-        ra.n_pts = np; ra.n_cur = n; ra.cap = P.cap; ra.local = 1; ra.check_ori = 0; ra.nnratio = P.nnratio;
-        ra.cands = (const Cand*)(d + o_cand); ra.ncand = (const int32_t*)(d + o_nc); ra.observed = (const uint8_t*)(d + o_ob);
-        ra.taken0 = frame_taken ? (const uint8_t*)(d + o_tk) : nullptr; ra.cur_kp = (const float4*)(d + o_kp);
-        ra.last_angle = nullptr; ra.overflow = (const int32_t*)(d + o_ovf); ra.st = (int32_t*)(d + o_st);
-        int32_t* kw = (int32_t*)(d + o_kw);
-        const size_t nk = (size_t)std::max(n, 1);
-        ra.claimMin = kw; ra.last = kw + nk; ra.removed = kw + 2 * nk;
-        ra.lister = (int32_t*)(d + o_lf); ra.fixed = (int32_t*)(d + o_lf) + nk;
-        ra.work = (int32_t*)(d + o_wl);
-        ra.top = (int4*)(d + o_top); ra.nusable = (int32_t*)(d + o_top + (size_t)std::max(np, 1) * 64);
-        ra.lds_keypoints = n <= kResolveLdsKeypoints && resolve_lds_ready() ? 1 : 0;
-        ra.mp = (int32_t*)(d + o_m); ra.out_n = (int32_t*)(d + o_ovf) + 1;
-        if (ok) {
-            if (ra.n_pts > 0) hipLaunchKernelGGL(k_resolve_init, dim3((ra.n_pts + 255) / 256), dim3(256), 0, s, ra);
-            hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), ra.lds_keypoints ? 8 * (size_t)n : 0,
-                               s, ra);
-        }
-        ok = ok && hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(h + o_ovf, d + o_ovf, o_m - o_ovf + (size_t)std::max(n, 1) * 4, hipMemcpyDeviceToHost, s) ==
-                 hipSuccess &&
-             hipStreamSynchronize(s) == hipSuccess;
-        if (!ok) return orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection(local) failed");
-        int32_t ovf = 0;
-        memcpy(&ovf, h + o_ovf, 4);
-        if (ovf > P.cap) {
-            P.cap = (ovf + 63) & ~63;
-            continue;
-        }
-        if (n) memcpy(match, h + o_m, (size_t)n * 4);
-        memcpy(n_matches, h + o_ovf + 4, 4);
-        return ORB_OK;
-    }
-    return orbgpu_fail(ORB_ERR_INTERNAL, "SearchByProjection(local) candidate capacity");
+    const int np = pts->n;
+    uint8_t *in_view, *bad, *observed;
+    float *proj, *view_cos, *depth;
+    int32_t* level;
+    uint4* desc;
+    return host_search<k_lmp_candidates_args>(
+        m, F, frame_taken, np, match, n_matches, "SearchByProjection(local map)", k_lmp_candidates,
+        [&](DevScratch& z) {
+            in_view = z.take<uint8_t>(np);
+            bad = z.take<uint8_t>(np);
+            observed = z.take<uint8_t>(np);
+            proj = z.take<float>(3 * (size_t)np);
+            view_cos = z.take<float>(np);
+            depth = z.take<float>(np);
+            level = z.take<int32_t>(np);
+            desc = z.take<uint4>(2 * (size_t)np);
+        },
+        [&](const HostCall& c, k_lmp_candidates_args& ca) {
+            c.put(in_view, pts->track_in_view, np);
+            c.put(bad, pts->is_bad, np);
+            c.put(observed, pts->observed, np);
+            c.put(proj, pts->track_proj, 3 * (size_t)np);
+            c.put(view_cos, pts->track_view_cos, np);
+            c.put(depth, pts->track_depth, np);
+            c.put(level, pts->track_level, np);
+            c.put(desc, pts->desc, (size_t)np * 32);
+            const float nnratio = orbgpu_matcher_nnratio(m);
+            const LocalParams P = make_local_params(F, th, far_points, th_far_points, F->n, np, c.cap, nnratio);
+            ca = k_lmp_candidates_args{P, in_view, bad, proj, view_cos, depth, level, desc, c.cur(), c.r.cands, c.r.ncand,
+                                       c.r.ovf, observed, c.taken, c.r.lf};
+            return make_resolve_args(c.r, np, F->n, c.cap, 1, 0, nnratio, observed, c.taken, c.kp4, nullptr, c.r.mp,
+                                     nullptr, nullptr);
+        });
 }
 
-namespace {
+// ---- device forms: single calls and the tracking chain's batches --------------------------------
 
-// the stream-ordered scratch of one device call
-struct DevScratch {
-    char* base = nullptr;
-    size_t off = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(base + off);
-        off = align256(off + std::max<size_t>(count, 1) * sizeof(T));
-        return p;
-    }
-};
+namespace {
 
 bool frame_device_ok(const orb_frame_device_t* F) {
     return F && F->kps_un && F->desc && F->n && F->cap > 0 && F->cap <= kResolveLdsKeypoints && F->nlevels > 0 &&
@@ -1387,104 +1206,197 @@ bool frame_device_ok(const orb_frame_device_t* F) {
            (reinterpret_cast<uintptr_t>(F->desc) & 15) == 0;
 }
 
-}  // namespace
-
-size_t orbgpu_sbp_frame_scratch_bytes(int C, int NL) {
-    DevScratch z;
-    z.take<int32_t>(2); z.take<float4>(C); z.take<int32_t>(kCells + 1); z.take<int32_t>(C);
-    z.take<int32_t>(C); z.take<uint8_t>(NL); z.take<int32_t>(NL); z.take<float>(NL); z.take<int32_t>(2 * (size_t)C);
-    z.take<int32_t>(4); z.take<Cand>((size_t)NL * C); z.take<int32_t>(NL); z.take<int32_t>(NL);
-    z.take<int32_t>(3 * (size_t)C); z.take<int32_t>(NL); z.take<int4>((kTop / 2) * (size_t)NL); z.take<int32_t>(NL);
-    return z.off;
+// the frame's grid, built by k_frame_prep: dims ([0] points, [1] keypoints) | kp4 | cells | cell_of
+struct GridScratch {
+    int32_t* dims;
+    float4* kp4;
+    int32_t* cell_off;
+    int32_t* cell_idx;
+    int32_t* cell_of;
+};
+GridScratch carve_grid(DevScratch& z, int C) {
+    GridScratch g;
+    g.dims = z.take<int32_t>(2);
+    g.kp4 = z.take<float4>(C);
+    g.cell_off = z.take<int32_t>(kCells + 1);
+    g.cell_idx = z.take<int32_t>(C);
+    g.cell_of = z.take<int32_t>(C);
+    return g;
 }
-
-extern "C" int orb_search_by_projection_frame_device(orb_matcher_t m, const orb_frame_device_t* cur,
-                                                     const orb_last_points_device_t* last, float th, int mono,
-                                                     int32_t* d_match, int32_t* d_n_matches, void* stream) {
-    return orbgpu_sbp_frame_device_scratch(m, cur, last, th, mono, d_match, d_n_matches, stream, nullptr);
+CurRecords<> cur_records(const orb_frame_device_t* F, const GridScratch& g) {
+    return CurRecords<>{g.kp4, F->u_right, (const uint4*)F->desc, g.cell_off, g.cell_idx};
 }
-
-namespace {
+// k_frame_prep's arguments; it also initialises the call's scratch words (dims0: ScratchInit)
+k_frame_prep_args frame_prep_args(const orb_frame_device_t* F, const GridScratch& g, const ResolveScratch& r,
+                                  int32_t* d_match, int dims0) {
+    const int C = F->cap;
+    const ScratchInit zi{r.lf, 2 * C, d_match, C, r.ovf, g.dims, dims0};
+    return k_frame_prep_args{F->kps_un, F->n, C, F->min_x, F->min_y, F->grid_inv_w, F->grid_inv_h, g.kp4,
+                             g.cell_off, g.cell_idx, g.cell_of, g.dims + 1, nullptr, zi};
+}
 
 // One frame's launches of a device SearchByProjection form, as argument blocks (the single-frame call
 // launches them by value, the batch copies them to the device and launches one grid row per frame).
-struct SbpFramePlan {
+// T: the overload (FrameSearch, LocalSearch below).
+template <class T>
+struct SbpPlan {
     k_frame_prep_args prep;
-    k_last_prep_args lprep;
-    k_proj_candidates_args cand;
+    typename T::PrepArgs pprep;
+    typename T::CandArgs cand;
     k_resolve_init_args init;
     k_resolve_rounds_args rounds;
-    int C, NL;
 };
 
-bool sbp_frame_args_ok(orb_matcher_t m, const orb_frame_device_t* cur, const orb_last_points_device_t* last,
-                       const int32_t* d_match, const int32_t* d_n_matches) {
-    return m && frame_device_ok(cur) && last && d_match && d_n_matches && last->n && last->cap >= 0 &&
-           (last->cap == 0 || (last->valid && last->observed && last->xyz && last->desc && last->kps_un)) &&
-           (reinterpret_cast<uintptr_t>(last->desc) & 15) == 0;
+// What the two overloads do not share: their points and call parameters, the argument check, the
+// scratch layout and the plan, the points' prep kernel and the three candidate kernels.
+struct FrameSearch {
+    using Points = orb_last_points_device_t;
+    using PrepArgs = k_last_prep_args;
+    using CandArgs = k_proj_candidates_args;
+    struct Call {
+        float th;
+        int mono;
+    };
+    static constexpr const char* kName = "SearchByProjection";
+    static constexpr auto k_prep = k_last_prep;
+    static constexpr auto k_prep_b = k_last_prep_b;
+    static constexpr auto k_cand = k_proj_candidates;
+    static constexpr auto k_cand_t_b = k_proj_candidates_t_b;
+    static void launch_cand_l_b(int B, int C, hipStream_t s, const CandArgs* ca, const k_resolve_init_args*) {
+        hipLaunchKernelGGL(k_proj_candidates_l_b, dim3(B), dim3(kCandLdsThreads), cand_lds_bytes(C), s, ca);
+    }
+    static int n_points(const Points* last) { return last->cap; }
+    static bool args_ok(orb_matcher_t m, const orb_frame_device_t* cur, const Points* last, const int32_t* d_match,
+                        const int32_t* d_n_matches) {
+        return m && frame_device_ok(cur) && last && d_match && d_n_matches && last->n && last->cap >= 0 &&
+               (last->cap == 0 || (last->valid && last->observed && last->xyz && last->desc && last->kps_un)) &&
+               (reinterpret_cast<uintptr_t>(last->desc) & 15) == 0;
+    }
+    // grid | the last frame's prepared points | candidates and resolver
+    struct Scratch {
+        GridScratch g;
+        uint8_t* valid2;
+        int32_t* loct;
+        float* lang;
+        ResolveScratch r;
+    };
+    static Scratch carve(DevScratch& z, int C, int NL) {
+        Scratch x;
+        x.g = carve_grid(z, C);
+        x.valid2 = z.take<uint8_t>(NL);
+        x.loct = z.take<int32_t>(NL);
+        x.lang = z.take<float>(NL);
+        x.r = carve_resolve(z, C, NL, C, false);
+        return x;
+    }
+    static void plan(orb_matcher_t m, const orb_frame_device_t* cur, const uint8_t*, const Points* last, const Call& call,
+                     int32_t* d_match, int32_t* d_n_matches, char* base, SbpPlan<FrameSearch>& pl) {
+        const int C = cur->cap, NL = last->cap;
+        DevScratch z;
+        z.base = base;
+        const Scratch x = carve(z, C, NL);
+        // cap = C: a point's candidates are distinct current keypoints, never more than the frame holds
+        const ProjParams P = make_proj_params(cur, last->Tcw, call.th, call.mono, 0, 0, C, orbgpu_matcher_check_ori(m));
+        pl.prep = frame_prep_args(cur, x.g, x.r, d_match, NL > 0 ? -1 : 0);
+        pl.pprep = k_last_prep_args{last->kps_un, last->valid, last->n, NL, cur->nlevels, x.valid2, x.loct, x.lang,
+                                    x.g.dims, nullptr};
+        pl.cand = k_proj_candidates_args{P, x.g.dims, x.valid2, last->xyz, (const uint4*)last->desc, x.loct,
+                                         cur_records(cur, x.g), x.r.cands, x.r.ncand, x.r.ovf, last->observed, x.r.lf};
+        pl.init.a = make_resolve_args(x.r, NL, C, C, 0, P.check_ori, 0.f, last->observed, nullptr, x.g.kp4, x.lang,
+                                      d_match, x.g.dims, d_n_matches);
+        pl.rounds.a = pl.init.a;
+    }
+};
+
+struct LocalSearch {
+    using Points = orb_local_points_device_t;
+    using PrepArgs = k_local_prep_args;
+    using CandArgs = k_lmp_candidates_args;
+    struct Call {
+        float th;
+        int far_points;
+        float th_far_points;
+    };
+    static constexpr const char* kName = "SearchByProjection(local map)";
+    static constexpr auto k_prep = k_local_prep;
+    static constexpr auto k_prep_b = k_local_prep_b;
+    static constexpr auto k_cand = k_lmp_candidates;
+    static constexpr auto k_cand_t_b = k_lmp_candidates_t_b;
+    // (ri: the frame's keypoint count, for the gated frames, is in the init block's dims)
+    static void launch_cand_l_b(int B, int C, hipStream_t s, const CandArgs* ca, const k_resolve_init_args* ri) {
+        hipLaunchKernelGGL(k_lmp_candidates_l_b, dim3(B), dim3(kCandLdsThreads), cand_lds_bytes(C), s, ca, ri);
+    }
+    static int n_points(const Points* pts) { return pts->n; }
+    static bool args_ok(orb_matcher_t m, const orb_frame_device_t* F, const Points* pts, const int32_t* d_match,
+                        const int32_t* d_n_matches) {
+        return m && frame_device_ok(F) && pts && pts->n >= 0 && d_match && d_n_matches &&
+               (pts->n == 0 || (pts->track_in_view && pts->is_bad && pts->observed && pts->track_proj && pts->track_view_cos &&
+                                pts->track_depth && pts->track_level && pts->desc)) &&
+               (reinterpret_cast<uintptr_t>(pts->desc) & 15) == 0;
+    }
+    // grid | the points' in-view flags with the level check | candidates and resolver
+    struct Scratch {
+        GridScratch g;
+        uint8_t* iv2;
+        ResolveScratch r;
+    };
+    static Scratch carve(DevScratch& z, int C, int np) {
+        Scratch x;
+        x.g = carve_grid(z, C);
+        x.iv2 = z.take<uint8_t>(np);
+        x.r = carve_resolve(z, C, np, C, false);
+        return x;
+    }
+    static void plan(orb_matcher_t m, const orb_frame_device_t* F, const uint8_t* d_frame_taken, const Points* pts,
+                     const Call& call, int32_t* d_match, int32_t* d_n_matches, char* base, SbpPlan<LocalSearch>& pl) {
+        const int C = F->cap, np = pts->n;
+        DevScratch z;
+        z.base = base;
+        const Scratch x = carve(z, C, np);
+        const LocalParams P = make_local_params(F, call.th, call.far_points, call.th_far_points, 0, np, C,
+                                                orbgpu_matcher_nnratio(m));
+        pl.prep = frame_prep_args(F, x.g, x.r, d_match, np);
+        pl.pprep = k_local_prep_args{pts->track_in_view, pts->track_level, np, F->nlevels, x.iv2};
+        pl.cand = k_lmp_candidates_args{P, x.iv2, pts->is_bad, pts->track_proj, pts->track_view_cos, pts->track_depth,
+                                        pts->track_level, (const uint4*)pts->desc, cur_records(F, x.g), x.r.cands,
+                                        x.r.ncand, x.r.ovf, pts->observed, d_frame_taken, x.r.lf};
+        pl.init.a = make_resolve_args(x.r, np, C, C, 1, 0, P.nnratio, pts->observed, d_frame_taken, x.g.kp4, nullptr,
+                                      d_match, x.g.dims, d_n_matches);
+        pl.rounds.a = pl.init.a;
+    }
+};
+
+template <class T>
+size_t sbp_scratch_bytes(int C, int np) {
+    DevScratch z;
+    T::carve(z, C, np);
+    return z.off;
 }
 
-void sbp_frame_plan(orb_matcher_t m, const orb_frame_device_t* cur, const orb_last_points_device_t* last, float th,
-                    int mono, int32_t* d_match, int32_t* d_n_matches, char* base, SbpFramePlan& pl) {
-    const int C = cur->cap, NL = last->cap;
-    pl.C = C;
-    pl.NL = NL;
-    ProjParams P{};
-    memcpy(P.Tcw, cur->Tcw, sizeof(P.Tcw));
-    P.min_x = cur->min_x; P.max_x = cur->max_x; P.min_y = cur->min_y; P.max_y = cur->max_y;
-    P.inv_w = cur->grid_inv_w; P.inv_h = cur->grid_inv_h;
-    P.fx = cur->fx; P.fy = cur->fy; P.cx = cur->cx; P.cy = cur->cy; P.bf = cur->bf; P.th = th;
-    for (int l = 0; l < cur->nlevels; ++l) P.scale[l] = cur->scale_factors[l];
-    P.n_cur = 0; P.n_last = 0; P.has_ur = cur->u_right != nullptr;
-    {   // twc = -R^T t, tlc = Tlw * twc (src:1960-1968), as the host form computes them
-        const float* T = cur->Tcw;
-        float twc[3], tlc[3];
-        for (int i = 0; i < 3; ++i) twc[i] = -std::fma(T[8 + i], T[11], std::fma(T[i], T[3], T[4 + i] * T[7]));
-        for (int i = 0; i < 3; ++i)
-            tlc[i] = std::fma(last->Tcw[4 * i + 2], twc[2], std::fma(last->Tcw[4 * i], twc[0], last->Tcw[4 * i + 1] * twc[1])) +
-                     last->Tcw[4 * i + 3];
-        P.bForward = tlc[2] > cur->b && !mono;
-        P.bBackward = -tlc[2] > cur->b && !mono;
+// A single device call: the wave candidate kernel.  scratch: the caller's (sbp_scratch_bytes), else
+// stream-ordered.
+template <class T>
+int sbp_device(orb_matcher_t m, const orb_frame_device_t* F, const uint8_t* d_frame_taken, const typename T::Points* pts,
+               const typename T::Call& call, int32_t* d_match, int32_t* d_n_matches, void* stream, void* scratch) {
+    if (!T::args_ok(m, F, pts, d_match, d_n_matches)) return sbp_fail(ORB_ERR_ARG, "bad ", T::kName, " device arguments");
+    hipStream_t s = (hipStream_t)stream;
+    const int C = F->cap, np = T::n_points(pts);
+    char* base = static_cast<char*>(scratch);
+    if (!base && hipMallocAsync(reinterpret_cast<void**>(&base), sbp_scratch_bytes<T>(C, np), s) != hipSuccess)
+        return orbgpu_fail(ORB_ERR_DEVICE, "hipMallocAsync failed");
+    SbpPlan<T> pl;
+    T::plan(m, F, d_frame_taken, pts, call, d_match, d_n_matches, base, pl);
+    hipLaunchKernelGGL(k_frame_prep, dim3(1), dim3(kPrepThreads), 0, s, pl.prep);
+    if (np > 0) {
+        hipLaunchKernelGGL(T::k_prep, dim3((np + 255) / 256), dim3(256), 0, s, pl.pprep);
+        hipLaunchKernelGGL(T::k_cand, dim3((np + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, s, pl.cand);
+        hipLaunchKernelGGL(k_resolve_init, dim3((np + 255) / 256), dim3(256), 0, s, pl.init.a);
     }
-    P.cap = C;  // a point's candidates are distinct current keypoints: never more than the frame holds
-    P.check_ori = orbgpu_matcher_check_ori(m);
-    // scratch: dims | kp4 | cells | cell_of | last prep | lister + fixed | overflow block | candidates |
-    // ncand | st | claimMin, last, removed | work list | top
-    DevScratch z;
-    z.base = base;
-    int32_t* dims = z.take<int32_t>(2);
-    float4* kp4 = z.take<float4>(C);
-    int32_t* cell_off = z.take<int32_t>(kCells + 1);
-    int32_t* cell_idx = z.take<int32_t>(C);
-    int32_t* cell_of = z.take<int32_t>(C);
-    uint8_t* valid2 = z.take<uint8_t>(NL);
-    int32_t* loct = z.take<int32_t>(NL);
-    float* lang = z.take<float>(NL);
-    int32_t* lf = z.take<int32_t>(2 * (size_t)C);
-    int32_t* ovf = z.take<int32_t>(4);
-    Cand* cands = z.take<Cand>((size_t)NL * C);
-    int32_t* nc = z.take<int32_t>(NL);
-    int32_t* st = z.take<int32_t>(NL);
-    int32_t* kw = z.take<int32_t>(3 * (size_t)C);
-    int32_t* wl = z.take<int32_t>(NL);
-    int4* top = z.take<int4>((kTop / 2) * (size_t)NL);
-    int32_t* nus = z.take<int32_t>(NL);
-    const ScratchInit zi{lf, 2 * C, d_match, C, ovf, dims, NL > 0 ? -1 : 0};
-    pl.prep = k_frame_prep_args{cur->kps_un, cur->n, C, cur->min_x, cur->min_y, cur->grid_inv_w, cur->grid_inv_h, kp4,
-                                cell_off, cell_idx, cell_of, dims + 1, nullptr, zi};
-    pl.lprep = k_last_prep_args{last->kps_un, last->valid, last->n, NL, cur->nlevels, valid2, loct, lang, dims, nullptr};
-    pl.cand = k_proj_candidates_args{P, dims, valid2, last->xyz, (const uint4*)last->desc, loct, kp4, cur->u_right,
-                                     (const uint4*)cur->desc, cell_off, cell_idx, cands, nc, ovf, last->observed, lf};
-    ResolveArgs ra{};
-    ra.n_pts = NL; ra.n_cur = C; ra.cap = C; ra.local = 0; ra.check_ori = P.check_ori; ra.nnratio = 0.f;
-    ra.cands = cands; ra.ncand = nc; ra.observed = last->observed; ra.taken0 = nullptr; ra.cur_kp = kp4;
-    ra.last_angle = lang; ra.overflow = ovf; ra.st = st;
-    ra.claimMin = kw; ra.last = kw + C; ra.removed = kw + 2 * (size_t)C;
-    ra.lister = lf; ra.fixed = lf + C; ra.work = wl; ra.top = top; ra.nusable = nus;
-    ra.lds_keypoints = resolve_lds_ready() ? 1 : 0;
-    ra.mp = d_match; ra.out_n = ovf + 1; ra.dims = dims; ra.out_user = d_n_matches;
-    pl.init.a = ra;
-    pl.rounds.a = ra;
+    hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), pl.rounds.a.lds_keypoints ? 8 * (size_t)C : 0, s,
+                       pl.rounds.a);
+    bool ok = hipGetLastError() == hipSuccess;
+    if (!scratch && hipFreeAsync(base, s) != hipSuccess) ok = false;
+    return ok ? ORB_OK : sbp_fail(ORB_ERR_DEVICE, "", T::kName, " device failed");
 }
 
 // Argument blocks of B frames into one host block (each kernel's B blocks contiguous, 256-B aligned),
@@ -1500,103 +1412,78 @@ struct ArgPacker {
     }
 };
 
-}  // namespace
-
-int orbgpu_sbp_frame_device_scratch(orb_matcher_t m, const orb_frame_device_t* cur, const orb_last_points_device_t* last,
-                                    float th, int mono, int32_t* d_match, int32_t* d_n_matches, void* stream,
-                                    void* scratch) {
-    if (!sbp_frame_args_ok(m, cur, last, d_match, d_n_matches))
-        return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection device arguments");
-    hipStream_t s = (hipStream_t)stream;
-    const int C = cur->cap, NL = last->cap;
-    char* base = static_cast<char*>(scratch);  // the caller's (orbgpu_sbp_frame_scratch_bytes), else stream-ordered
-    if (!base && hipMallocAsync(reinterpret_cast<void**>(&base), orbgpu_sbp_frame_scratch_bytes(C, NL), s) != hipSuccess)
-        return orbgpu_fail(ORB_ERR_DEVICE, "hipMallocAsync failed");
-    SbpFramePlan pl;
-    sbp_frame_plan(m, cur, last, th, mono, d_match, d_n_matches, base, pl);
-    const k_frame_prep_args& fp = pl.prep;
-    hipLaunchKernelGGL(k_frame_prep, dim3(1), dim3(kPrepThreads), 0, s, fp.kps, fp.n_ptr, fp.cap, fp.min_x, fp.min_y,
-                       fp.inv_w, fp.inv_h, fp.kp4, fp.cell_off, fp.cell_idx, fp.cell_of, fp.n_out0, fp.n_out1, fp.z);
-    if (NL > 0) {
-        const k_last_prep_args& lp = pl.lprep;
-        hipLaunchKernelGGL(k_last_prep, dim3((NL + 255) / 256), dim3(256), 0, s, lp.kps, lp.valid, lp.n_ptr, lp.cap,
-                           lp.nlevels, lp.valid2, lp.octave, lp.angle, lp.n_out0, lp.n_out1);
-        const k_proj_candidates_args& c = pl.cand;
-        if (cand_thread_mode(false))
-            hipLaunchKernelGGL(k_proj_candidates_t, dim3((NL + kCandThreads - 1) / kCandThreads), dim3(kCandThreads), 0,
-                               s, c);
-        else
-            hipLaunchKernelGGL(k_proj_candidates, dim3((NL + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, s,
-                               c.P, c.n_dev, c.valid, c.xyz, c.mp_desc, c.last_octave, c.cur_kp, c.cur_ur, c.cur_desc,
-                               c.cell_off, c.cell_idx, c.cands, c.ncand, c.overflow, c.observed, c.lister);
-        hipLaunchKernelGGL(k_resolve_init, dim3((NL + 255) / 256), dim3(256), 0, s, pl.init.a);
-    }
-    hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), pl.rounds.a.lds_keypoints ? 8 * (size_t)C : 0, s,
-                       pl.rounds.a);
-    bool ok = hipGetLastError() == hipSuccess;
-    if (!scratch && hipFreeAsync(base, s) != hipSuccess) ok = false;
-    return ok ? ORB_OK : orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection device failed");
-}
-
-int orbgpu_sbp_frame_batch(orb_matcher_t m, int B, const orb_frame_device_t* const* cur,
-                           const orb_last_points_device_t* const* last, float th, int mono, int32_t* const* d_match,
-                           int32_t* const* d_n_matches, char* scratch, size_t stride, void* d_args, void* h_args,
-                           size_t args_cap, void* stream) {
-    if (B <= 0 || !scratch || !d_args || !h_args) return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection batch arguments");
+// A batch: every stage one launch, frame b on grid row b (the LDS-staged candidates: workgroup b).
+// d_frame_taken may be NULL (no frame has flags).
+template <class T>
+int sbp_batch(orb_matcher_t m, int B, const orb_frame_device_t* const* F, const uint8_t* const* d_frame_taken,
+              const typename T::Points* const* pts, const typename T::Call& call, int32_t* const* d_match,
+              int32_t* const* d_n_matches, char* scratch, size_t stride, void* d_args, void* h_args, size_t args_cap,
+              void* stream) {
+    if (B <= 0 || !scratch || !d_args || !h_args) return sbp_fail(ORB_ERR_ARG, "bad ", T::kName, " batch arguments");
     hipStream_t s = (hipStream_t)stream;
     std::vector<k_frame_prep_args> fp(B);
-    std::vector<k_last_prep_args> lp(B);
-    std::vector<k_proj_candidates_args> ca(B);
+    std::vector<typename T::PrepArgs> pp(B);
+    std::vector<typename T::CandArgs> ca(B);
     std::vector<k_resolve_init_args> ri(B);
     std::vector<k_resolve_rounds_args> rr(B);
-    int C = -1, maxNL = 0;
+    int C = -1, maxNp = 0;
     for (int b = 0; b < B; ++b) {
-        if (!sbp_frame_args_ok(m, cur[b], last[b], d_match[b], d_n_matches[b]) || (C >= 0 && cur[b]->cap != C) ||
-            orbgpu_sbp_frame_scratch_bytes(cur[b]->cap, last[b]->cap) > stride)
-            return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection batch frame (caps must agree, scratch stride)");
-        C = cur[b]->cap;
-        SbpFramePlan pl;
-        sbp_frame_plan(m, cur[b], last[b], th, mono, d_match[b], d_n_matches[b], scratch + (size_t)b * stride, pl);
-        fp[b] = pl.prep; lp[b] = pl.lprep; ca[b] = pl.cand; ri[b] = pl.init; rr[b] = pl.rounds;
-        maxNL = std::max(maxNL, pl.NL);
+        if (!T::args_ok(m, F[b], pts[b], d_match[b], d_n_matches[b]) || (C >= 0 && F[b]->cap != C) ||
+            sbp_scratch_bytes<T>(F[b]->cap, T::n_points(pts[b])) > stride)
+            return sbp_fail(ORB_ERR_ARG, "bad ", T::kName, " batch frame (caps must agree, scratch stride)");
+        C = F[b]->cap;
+        SbpPlan<T> pl;
+        T::plan(m, F[b], d_frame_taken ? d_frame_taken[b] : nullptr, pts[b], call, d_match[b], d_n_matches[b],
+                scratch + (size_t)b * stride, pl);
+        fp[b] = pl.prep; pp[b] = pl.pprep; ca[b] = pl.cand; ri[b] = pl.init; rr[b] = pl.rounds;
+        maxNp = std::max(maxNp, T::n_points(pts[b]));
     }
     ArgPacker pk;
-    const size_t o_fp = pk.add(fp), o_lp = pk.add(lp), o_ca = pk.add(ca), o_ri = pk.add(ri), o_rr = pk.add(rr);
-    if (pk.host.size() > args_cap) return orbgpu_fail(ORB_ERR_ARG, "SearchByProjection batch: argument area too small");
+    const size_t o_fp = pk.add(fp), o_pp = pk.add(pp), o_ca = pk.add(ca), o_ri = pk.add(ri), o_rr = pk.add(rr);
+    if (pk.host.size() > args_cap) return sbp_fail(ORB_ERR_ARG, "", T::kName, " batch: argument area too small");
     char* d = static_cast<char*>(d_args);
     memcpy(h_args, pk.host.data(), pk.host.size());  // pinned staging: the copy reads it when the stream runs it
     if (hipMemcpyAsync(d, h_args, pk.host.size(), hipMemcpyHostToDevice, s) != hipSuccess)
         return orbgpu_fail(ORB_ERR_DEVICE, "batch argument upload failed");
     hipLaunchKernelGGL(k_frame_prep_b, dim3(1, B), dim3(kPrepThreads), 0, s, (const k_frame_prep_args*)(d + o_fp));
-    if (maxNL > 0) {  // grids sized for the largest frame; the kernels bound themselves by their own counts
-        hipLaunchKernelGGL(k_last_prep_b, dim3((maxNL + 255) / 256, B), dim3(256), 0, s,
-                           (const k_last_prep_args*)(d + o_lp));
+    if (maxNp > 0) {  // grids sized for the largest frame; the kernels bound themselves by their own counts
+        hipLaunchKernelGGL(T::k_prep_b, dim3((maxNp + 255) / 256, B), dim3(256), 0, s,
+                           (const typename T::PrepArgs*)(d + o_pp));
         if (cand_lds_mode(C))
-            hipLaunchKernelGGL(k_proj_candidates_l_b, dim3(B), dim3(kCandLdsThreads), cand_lds_bytes(C), s,
-                               (const k_proj_candidates_args*)(d + o_ca));
-        else if (cand_thread_mode(true))
-            hipLaunchKernelGGL(k_proj_candidates_t_b, dim3((maxNL + kCandThreads - 1) / kCandThreads, B), dim3(kCandThreads), 0,
-                               s, (const k_proj_candidates_args*)(d + o_ca));
+            T::launch_cand_l_b(B, C, s, (const typename T::CandArgs*)(d + o_ca), (const k_resolve_init_args*)(d + o_ri));
         else
-            hipLaunchKernelGGL(k_proj_candidates_b, dim3((maxNL + kCandWaves - 1) / kCandWaves, B), dim3(64 * kCandWaves), 0, s,
-                               (const k_proj_candidates_args*)(d + o_ca));
-        hipLaunchKernelGGL(k_resolve_init_b, dim3((maxNL + 255) / 256, B), dim3(256), 0, s,
+            hipLaunchKernelGGL(T::k_cand_t_b, dim3((maxNp + kCandThreads - 1) / kCandThreads, B), dim3(kCandThreads), 0, s,
+                               (const typename T::CandArgs*)(d + o_ca));
+        hipLaunchKernelGGL(k_resolve_init_b, dim3((maxNp + 255) / 256, B), dim3(256), 0, s,
                            (const k_resolve_init_args*)(d + o_ri));
     }
     hipLaunchKernelGGL(k_resolve_rounds_b, dim3(1, B), dim3(kResolveThreads), rr[0].a.lds_keypoints ? 8 * (size_t)C : 0, s,
                        (const k_resolve_rounds_args*)(d + o_rr));
-    return hipGetLastError() == hipSuccess ? ORB_OK : orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection batch launch failed");
+    return hipGetLastError() == hipSuccess ? ORB_OK : sbp_fail(ORB_ERR_DEVICE, "", T::kName, " batch launch failed");
 }
 
-size_t orbgpu_sbp_local_scratch_bytes(int C, int np) {
-    DevScratch z;
-    z.take<int32_t>(2); z.take<float4>(C); z.take<int32_t>(kCells + 1); z.take<int32_t>(C);
-    z.take<int32_t>(C); z.take<uint8_t>(np); z.take<int32_t>(2 * (size_t)C); z.take<int32_t>(4);
-    z.take<Cand>((size_t)np * C); z.take<int32_t>(np); z.take<int32_t>(np); z.take<int32_t>(3 * (size_t)C);
-    z.take<int32_t>(np); z.take<int4>((kTop / 2) * (size_t)np); z.take<int32_t>(np);
-    return z.off;
+}  // namespace
+
+size_t orbgpu_sbp_frame_scratch_bytes(int C, int NL) { return sbp_scratch_bytes<FrameSearch>(C, NL); }
+size_t orbgpu_sbp_local_scratch_bytes(int C, int np) { return sbp_scratch_bytes<LocalSearch>(C, np); }
+
+int orbgpu_sbp_frame_device_scratch(orb_matcher_t m, const orb_frame_device_t* cur, const orb_last_points_device_t* last,
+                                    float th, int mono, int32_t* d_match, int32_t* d_n_matches, void* stream,
+                                    void* scratch) {
+    return sbp_device<FrameSearch>(m, cur, nullptr, last, {th, mono}, d_match, d_n_matches, stream, scratch);
+}
+int orbgpu_sbp_local_device_scratch(orb_matcher_t m, const orb_frame_device_t* F, const uint8_t* d_frame_taken,
+                                    const orb_local_points_device_t* pts, float th, int far_points, float th_far_points,
+                                    int32_t* d_match, int32_t* d_n_matches, void* stream, void* scratch) {
+    return sbp_device<LocalSearch>(m, F, d_frame_taken, pts, {th, far_points, th_far_points}, d_match, d_n_matches, stream,
+                                   scratch);
 }
 
+extern "C" int orb_search_by_projection_frame_device(orb_matcher_t m, const orb_frame_device_t* cur,
+                                                     const orb_last_points_device_t* last, float th, int mono,
+                                                     int32_t* d_match, int32_t* d_n_matches, void* stream) {
+    return orbgpu_sbp_frame_device_scratch(m, cur, last, th, mono, d_match, d_n_matches, stream, nullptr);
+}
 extern "C" int orb_search_by_projection_local_device(orb_matcher_t m, const orb_frame_device_t* F,
                                                      const uint8_t* d_frame_taken, const orb_local_points_device_t* pts,
                                                      float th, int far_points, float th_far_points, int32_t* d_match,
@@ -1605,163 +1492,17 @@ extern "C" int orb_search_by_projection_local_device(orb_matcher_t m, const orb_
                                            stream, nullptr);
 }
 
-namespace {
-
-struct SbpLocalPlan {
-    k_frame_prep_args prep;
-    k_local_prep_args lprep;
-    k_lmp_candidates_args cand;
-    k_resolve_init_args init;
-    k_resolve_rounds_args rounds;
-    int C, np;
-};
-
-bool sbp_local_args_ok(orb_matcher_t m, const orb_frame_device_t* F, const orb_local_points_device_t* pts,
-                       const int32_t* d_match, const int32_t* d_n_matches) {
-    return m && frame_device_ok(F) && pts && pts->n >= 0 && d_match && d_n_matches &&
-           (pts->n == 0 || (pts->track_in_view && pts->is_bad && pts->observed && pts->track_proj && pts->track_view_cos &&
-                            pts->track_depth && pts->track_level && pts->desc)) &&
-           (reinterpret_cast<uintptr_t>(pts->desc) & 15) == 0;
+int orbgpu_sbp_frame_batch(orb_matcher_t m, int B, const orb_frame_device_t* const* cur,
+                           const orb_last_points_device_t* const* last, float th, int mono, int32_t* const* d_match,
+                           int32_t* const* d_n_matches, char* scratch, size_t stride, void* d_args, void* h_args,
+                           size_t args_cap, void* stream) {
+    return sbp_batch<FrameSearch>(m, B, cur, nullptr, last, {th, mono}, d_match, d_n_matches, scratch, stride, d_args,
+                                  h_args, args_cap, stream);
 }
-
-void sbp_local_plan(orb_matcher_t m, const orb_frame_device_t* F, const uint8_t* d_frame_taken,
-                    const orb_local_points_device_t* pts, float th, int far_points, float th_far_points, int32_t* d_match,
-                    int32_t* d_n_matches, char* base, SbpLocalPlan& pl) {
-    const int C = F->cap, np = pts->n;
-    pl.C = C;
-    pl.np = np;
-    LocalParams P{};
-    P.min_x = F->min_x; P.min_y = F->min_y; P.inv_w = F->grid_inv_w; P.inv_h = F->grid_inv_h;
-    P.th = th; P.th_far = th_far_points;
-    for (int l = 0; l < F->nlevels; ++l) P.scale[l] = F->scale_factors[l];
-    P.n_cur = 0; P.n_pts = np; P.has_ur = F->u_right != nullptr; P.far = far_points ? 1 : 0; P.nlevels = F->nlevels;
-    P.cap = C;
-    P.nnratio = orbgpu_matcher_nnratio(m);
-    DevScratch z;
-    z.base = base;
-    int32_t* dims = z.take<int32_t>(2);
-    float4* kp4 = z.take<float4>(C);
-    int32_t* cell_off = z.take<int32_t>(kCells + 1);
-    int32_t* cell_idx = z.take<int32_t>(C);
-    int32_t* cell_of = z.take<int32_t>(C);
-    uint8_t* iv2 = z.take<uint8_t>(np);
-    int32_t* lf = z.take<int32_t>(2 * (size_t)C);
-    int32_t* ovf = z.take<int32_t>(4);
-    Cand* cands = z.take<Cand>((size_t)np * C);
-    int32_t* nc = z.take<int32_t>(np);
-    int32_t* st = z.take<int32_t>(np);
-    int32_t* kw = z.take<int32_t>(3 * (size_t)C);
-    int32_t* wl = z.take<int32_t>(np);
-    int4* top = z.take<int4>((kTop / 2) * (size_t)np);
-    int32_t* nus = z.take<int32_t>(np);
-    const ScratchInit zi{lf, 2 * C, d_match, C, ovf, dims, np};
-    pl.prep = k_frame_prep_args{F->kps_un, F->n, C, F->min_x, F->min_y, F->grid_inv_w, F->grid_inv_h, kp4, cell_off,
-                                cell_idx, cell_of, dims + 1, nullptr, zi};
-    pl.lprep = k_local_prep_args{pts->track_in_view, pts->track_level, np, F->nlevels, iv2};
-    pl.cand = k_lmp_candidates_args{P, iv2, pts->is_bad, pts->track_proj, pts->track_view_cos, pts->track_depth,
-                                    pts->track_level, (const uint4*)pts->desc, kp4, F->u_right, (const uint4*)F->desc,
-                                    cell_off, cell_idx, cands, nc, ovf, pts->observed, d_frame_taken, lf};
-    ResolveArgs ra{};
-    ra.n_pts = np; ra.n_cur = C; ra.cap = C; ra.local = 1; ra.check_ori = 0; ra.nnratio = P.nnratio;
-    ra.cands = cands; ra.ncand = nc; ra.observed = pts->observed; ra.taken0 = d_frame_taken; ra.cur_kp = kp4;
-    ra.last_angle = nullptr; ra.overflow = ovf; ra.st = st;
-    ra.claimMin = kw; ra.last = kw + C; ra.removed = kw + 2 * (size_t)C;
-    ra.lister = lf; ra.fixed = lf + C; ra.work = wl; ra.top = top; ra.nusable = nus;
-    ra.lds_keypoints = resolve_lds_ready() ? 1 : 0;
-    ra.mp = d_match; ra.out_n = ovf + 1; ra.dims = dims; ra.out_user = d_n_matches;
-    pl.init.a = ra;
-    pl.rounds.a = ra;
-}
-
-}  // namespace
-
-int orbgpu_sbp_local_device_scratch(orb_matcher_t m, const orb_frame_device_t* F, const uint8_t* d_frame_taken,
-                                    const orb_local_points_device_t* pts, float th, int far_points, float th_far_points,
-                                    int32_t* d_match, int32_t* d_n_matches, void* stream, void* scratch) {
-    if (!sbp_local_args_ok(m, F, pts, d_match, d_n_matches))
-        return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection(local map) device arguments");
-    hipStream_t s = (hipStream_t)stream;
-    const int C = F->cap, np = pts->n;
-    char* base = static_cast<char*>(scratch);  // the caller's (orbgpu_sbp_local_scratch_bytes), else stream-ordered
-    if (!base && hipMallocAsync(reinterpret_cast<void**>(&base), orbgpu_sbp_local_scratch_bytes(C, np), s) != hipSuccess)
-        return orbgpu_fail(ORB_ERR_DEVICE, "hipMallocAsync failed");
-    SbpLocalPlan pl;
-    sbp_local_plan(m, F, d_frame_taken, pts, th, far_points, th_far_points, d_match, d_n_matches, base, pl);
-    const k_frame_prep_args& fp = pl.prep;
-    hipLaunchKernelGGL(k_frame_prep, dim3(1), dim3(kPrepThreads), 0, s, fp.kps, fp.n_ptr, fp.cap, fp.min_x, fp.min_y,
-                       fp.inv_w, fp.inv_h, fp.kp4, fp.cell_off, fp.cell_idx, fp.cell_of, fp.n_out0, fp.n_out1, fp.z);
-    if (np > 0) {
-        const k_local_prep_args& lp = pl.lprep;
-        hipLaunchKernelGGL(k_local_prep, dim3((np + 255) / 256), dim3(256), 0, s, lp.in_view, lp.level, lp.n, lp.nlevels,
-                           lp.in_view2);
-        const k_lmp_candidates_args& c = pl.cand;
-        if (cand_thread_mode(false))
-            hipLaunchKernelGGL(k_lmp_candidates_t, dim3((np + kCandThreads - 1) / kCandThreads), dim3(kCandThreads), 0,
-                               s, c);
-        else
-            hipLaunchKernelGGL(k_lmp_candidates, dim3((np + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, s,
-                               c.P, c.in_view, c.bad, c.proj, c.view_cos, c.depth, c.level, c.mp_desc, c.cur_kp, c.cur_ur,
-                               c.cur_desc, c.cell_off, c.cell_idx, c.cands, c.ncand, c.overflow, c.observed, c.taken0,
-                               c.lister);
-        hipLaunchKernelGGL(k_resolve_init, dim3((np + 255) / 256), dim3(256), 0, s, pl.init.a);
-    }
-    hipLaunchKernelGGL(k_resolve_rounds, dim3(1), dim3(kResolveThreads), pl.rounds.a.lds_keypoints ? 8 * (size_t)C : 0, s,
-                       pl.rounds.a);
-    bool ok = hipGetLastError() == hipSuccess;
-    if (!scratch && hipFreeAsync(base, s) != hipSuccess) ok = false;
-    return ok ? ORB_OK : orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection(local) device failed");
-}
-
 int orbgpu_sbp_local_batch(orb_matcher_t m, int B, const orb_frame_device_t* const* F, const uint8_t* const* d_frame_taken,
                            const orb_local_points_device_t* const* pts, float th, int far_points, float th_far_points,
                            int32_t* const* d_match, int32_t* const* d_n_matches, char* scratch, size_t stride,
                            void* d_args, void* h_args, size_t args_cap, void* stream) {
-    if (B <= 0 || !scratch || !d_args || !h_args)
-        return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection(local) batch arguments");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<k_frame_prep_args> fp(B);
-    std::vector<k_local_prep_args> lp(B);
-    std::vector<k_lmp_candidates_args> ca(B);
-    std::vector<k_resolve_init_args> ri(B);
-    std::vector<k_resolve_rounds_args> rr(B);
-    int C = -1, maxNp = 0;
-    for (int b = 0; b < B; ++b) {
-        if (!sbp_local_args_ok(m, F[b], pts[b], d_match[b], d_n_matches[b]) || (C >= 0 && F[b]->cap != C) ||
-            orbgpu_sbp_local_scratch_bytes(F[b]->cap, pts[b]->n) > stride)
-            return orbgpu_fail(ORB_ERR_ARG, "bad SearchByProjection(local) batch frame (caps must agree, scratch stride)");
-        C = F[b]->cap;
-        SbpLocalPlan pl;
-        sbp_local_plan(m, F[b], d_frame_taken[b], pts[b], th, far_points, th_far_points, d_match[b], d_n_matches[b],
-                       scratch + (size_t)b * stride, pl);
-        fp[b] = pl.prep; lp[b] = pl.lprep; ca[b] = pl.cand; ri[b] = pl.init; rr[b] = pl.rounds;
-        maxNp = std::max(maxNp, pl.np);
-    }
-    ArgPacker pk;
-    const size_t o_fp = pk.add(fp), o_lp = pk.add(lp), o_ca = pk.add(ca), o_ri = pk.add(ri), o_rr = pk.add(rr);
-    if (pk.host.size() > args_cap)
-        return orbgpu_fail(ORB_ERR_ARG, "SearchByProjection(local) batch: argument area too small");
-    char* d = static_cast<char*>(d_args);
-    memcpy(h_args, pk.host.data(), pk.host.size());  // pinned staging: the copy reads it when the stream runs it
-    if (hipMemcpyAsync(d, h_args, pk.host.size(), hipMemcpyHostToDevice, s) != hipSuccess)
-        return orbgpu_fail(ORB_ERR_DEVICE, "batch argument upload failed");
-    hipLaunchKernelGGL(k_frame_prep_b, dim3(1, B), dim3(kPrepThreads), 0, s, (const k_frame_prep_args*)(d + o_fp));
-    if (maxNp > 0) {
-        hipLaunchKernelGGL(k_local_prep_b, dim3((maxNp + 255) / 256, B), dim3(256), 0, s,
-                           (const k_local_prep_args*)(d + o_lp));
-        if (cand_lds_mode(C))  // (the frame's keypoint count, for the gated frames: the init block's dims)
-            hipLaunchKernelGGL(k_lmp_candidates_l_b, dim3(B), dim3(kCandLdsThreads), cand_lds_bytes(C), s,
-                               (const k_lmp_candidates_args*)(d + o_ca), (const k_resolve_init_args*)(d + o_ri));
-        else if (cand_thread_mode(true))
-            hipLaunchKernelGGL(k_lmp_candidates_t_b, dim3((maxNp + kCandThreads - 1) / kCandThreads, B), dim3(kCandThreads), 0,
-                               s, (const k_lmp_candidates_args*)(d + o_ca));
-        else
-            hipLaunchKernelGGL(k_lmp_candidates_b, dim3((maxNp + kCandWaves - 1) / kCandWaves, B), dim3(64 * kCandWaves), 0, s,
-                               (const k_lmp_candidates_args*)(d + o_ca));
-        hipLaunchKernelGGL(k_resolve_init_b, dim3((maxNp + 255) / 256, B), dim3(256), 0, s,
-                           (const k_resolve_init_args*)(d + o_ri));
-    }
-    hipLaunchKernelGGL(k_resolve_rounds_b, dim3(1, B), dim3(kResolveThreads), rr[0].a.lds_keypoints ? 8 * (size_t)C : 0, s,
-                       (const k_resolve_rounds_args*)(d + o_rr));
-    return hipGetLastError() == hipSuccess ? ORB_OK
-                                           : orbgpu_fail(ORB_ERR_DEVICE, "SearchByProjection(local) batch launch failed");
+    return sbp_batch<LocalSearch>(m, B, F, d_frame_taken, pts, {th, far_points, th_far_points}, d_match, d_n_matches,
+                                  scratch, stride, d_args, h_args, args_cap, stream);
 }

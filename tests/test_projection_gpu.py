@@ -1,5 +1,7 @@
-"""GPU parity of SearchByProjection(CurrentFrame, LastFrame, th, bMono) (k_proj_candidates +
-k_proj_resolve) against the oracle: bit-exact assignments and match counts, including contested
+"""GPU parity of SearchByProjection(CurrentFrame, LastFrame, th, bMono) and of the local-map overload
+(the host forms: the wave-per-point k_proj_candidates / k_lmp_candidates, then k_resolve_init +
+k_resolve_rounds; the batches' thread-per-point forms are tests/test_tracking_chain_gpu.py's) against
+the oracle: bit-exact assignments and match counts, including contested
 keypoints (the in-order 'already holds an observed map point' rule), mono/stereo, forward/backward
 motion and the orientation filter."""
 from __future__ import annotations
