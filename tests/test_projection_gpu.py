@@ -68,6 +68,10 @@ def test_search_by_projection_large_paths(pkg, oracle, synth):
     n, got = m.SearchByProjection(F, P, 10, False, 10.0, taken)
     rn, exp = oracle.search_by_projection_local(F, P, 10, False, 10.0, 0.8, taken)
     assert n == rn and np.array_equal(got, exp), f"{n} vs {rn}, {int((got != exp).sum())} differing"
+    # that the scene takes the path, shown on the second reference (tests/projection_ref.py)
+    from projection_ref import search_local
+    r = search_local(F, P, 10, False, 10.0, 0.8, taken)
+    assert r.n_affected > 2048 and r.n == rn and np.array_equal(r.assign, exp)
     cur, last = synth.tracking_pair(n_points=1500, clutter=17000, seed=62)
     C, L = pkg.Frame(**cur), pkg.Frame(**last)
     assert C.N > 16384
