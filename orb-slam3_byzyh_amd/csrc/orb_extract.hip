@@ -1957,21 +1957,160 @@ static_assert(kDescWords >= (kPR + 1) * kPRW + 1, "patch + the last pair's odd r
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr f32x2 kRound2 = {12582912.0f, 12582912.0f};  // 1.5 * 2^23: v + it has ulp 1 (|v| < 2^22)
-constexpr int kRoundBits = 0x4B400000;                 // its bit pattern
+constexpr uint32_t kRoundBits = 0x4B400000u;           // its bit pattern
 
-// Vertical 7-tap pass at one sample (r, c), |r|, |c| <= 18 from the keypoint: blurred row i = r + 18
-// reads sum rows i .. i+6, i.e. the 4 row pairs from i >> 1 (odd i: the first pair's high half).
-__device__ __forceinline__ int blur_sample(const uint32_t* __restrict__ H, int r, int c) {
-    // (the masks are no-ops for |r|, |c| <= 18; they bound the range so the offsets stay 24-bit
-    // multiplies and the four reads fold into two ds_read2_b32)
-    const unsigned i = (unsigned)(r + 18) & 63u, cc = (unsigned)(c + 18) & 63u;
-    const uint32_t* p = H + __umul24(i >> 1, (unsigned)kHPW) + cc;
-    const bool odd = (i & 1) != 0;
+// ---- The horizontal pass's item list.  A rounded sample (r, c) is the rotation of a pattern point
+// (x, y), x^2 + y^2 <= kPatR2, so (|r| - 1/2)^2 + (|c| - 1/2)^2 <= kPatR2 up to the float error of
+// the rotation (< 1e-5 px).  In units of 1/4 the left side is a sum of two odd squares: the first
+// value above 4 * 338 = 1352 is 1354 = 27^2 + 25^2, so the bound 4 * kPatR2 + 1 admits exactly the
+// reachable cells with a margin of 1/4 px^2, four orders above that error.  A sample reads sum rows
+// r + 18 .. r + 24 at column c + 18; an item (pair j, quad q) holds rows 2j, 2j + 1, columns 4q ..
+// 4q + 3.  The list keeps the items some reachable sample reads, by descending pair, padded to whole
+// rounds of 32 lanes with copies of its last item (the copy writes the same words again).
+constexpr int pattern_r2_max() {
+    int m = 0;
+    for (int k = 0; k < 512; ++k) {
+        const int x = kPatternSrc[2 * k], y = kPatternSrc[2 * k + 1], d = x * x + y * y;
+        if (x < -18 || x > 18 || y < -18 || y > 18) return -1;
+        m = d > m ? d : m;
+    }
+    return m;
+}
+constexpr int kPatR2 = pattern_r2_max();
+static_assert(kPatR2 == 338, "rBRIEF pattern radius: the patch (43 x 43) and the sums (43 x 37) are sized for 18 px");
+constexpr bool sample_reachable(int r, int c) {
+    const int u = 2 * (r < 0 ? -r : r) - 1, v = 2 * (c < 0 ? -c : c) - 1;
+    return (u > 0 ? u * u : 0) + (v > 0 ? v * v : 0) <= 4 * kPatR2 + 1;
+}
+struct HItemNeed { bool need[kHP][10]; int n; };
+constexpr HItemNeed hitem_need() {
+    HItemNeed t{};
+    for (int r = -18; r <= 18; ++r)
+        for (int c = -18; c <= 18; ++c)
+            if (sample_reachable(r, c))
+                for (int k = 0; k < 7; ++k) t.need[(r + 18 + k) >> 1][(c + 18) >> 2] = true;
+    for (int j = 0; j < kHP; ++j)
+        for (int q = 0; q < 10; ++q) t.n += t.need[j][q];
+    return t;
+}
+constexpr int kHItems = hitem_need().n, kHRounds = (kHItems + 31) / 32;
+// item = read byte offset (patch row 2j, dword q) | write byte offset (pair j, words 4q ..) << 16
+struct HItemTable { uint32_t w[kHRounds][32]; };
+constexpr uint32_t hitem_word(int j, int q) { return (uint32_t)(4 * (2 * j * kPRW + q)) | (uint32_t)(4 * (j * kHPW + 4 * q)) << 16; }
+constexpr HItemTable make_hitems() {
+    const HItemNeed nd = hitem_need();
+    HItemTable t{};
+    int n = 0;
+    uint32_t last = 0;
+    for (int j = kHP - 1; j >= 0; --j)
+        for (int q = 9; q >= 0; --q)
+            if (nd.need[j][q]) { last = hitem_word(j, q); t.w[n >> 5][n & 31] = last; ++n; }
+    for (; n < kHRounds * 32; ++n) t.w[n >> 5][n & 31] = last;
+    return t;
+}
+// Coverage: every sum word that a reachable sample's vertical pass weights is written by some item.
+constexpr bool hitems_cover() {
+    const HItemTable t = make_hitems();
+    bool wr[kHP][10] = {};
+    for (int i = 0; i < kHRounds * 32; ++i) {
+        const int o = (int)(t.w[i >> 5][i & 31] >> 16) / 4;
+        wr[o / kHPW][(o % kHPW) / 4] = true;
+    }
+    for (int r = -18; r <= 18; ++r)
+        for (int c = -18; c <= 18; ++c)
+            if (sample_reachable(r, c))
+                for (int k = 0; k < 7; ++k)
+                    if (!wr[(r + 18 + k) >> 1][(c + 18) >> 2]) return false;
+    return true;
+}
+// In place: an item reads bytes [rd, rd + 16) of patch rows 2j and 2j + 1 and writes 16 bytes at wr.
+// No item of a later round may read what an earlier round wrote (within a round the reads precede
+// the writes: one wave, LDS in order), and no item may write outside the keypoint's region.
+constexpr bool hitems_in_place() {
+    const HItemTable t = make_hitems();
+    for (int a = 0; a < kHRounds * 32; ++a) {
+        const int wa = (int)(t.w[a >> 5][a & 31] >> 16);
+        if (wa + 16 > 4 * kDescWords) return false;
+        for (int b = (a | 31) + 1; b < kHRounds * 32; ++b) {
+            const int rb = (int)(t.w[b >> 5][b & 31] & 0xffff);
+            for (int rr = 0; rr < 2; ++rr)
+                if (wa < rb + 4 * rr * kPRW + 16 && rb + 4 * rr * kPRW < wa + 16) return false;
+        }
+    }
+    return true;
+}
+static_assert(kHItems == 189 && kHRounds == 6, "items a sample can reach (of 22 x 10): six rounds of 32 lanes");
+static_assert(hitems_cover(), "every reachable sample's 7 sum rows are produced");
+static_assert(hitems_in_place(), "the compacted order never reads a patch byte that an earlier round overwrote");
+__constant__ HItemTable c_hitems = make_hitems();
+
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_addr(const uint32_t* p) { return (uint32_t)(uintptr_t)(const lds_u32*)p; }
+__device__ __forceinline__ lds_u32* lds_at(uint32_t a) { return (lds_u32*)(uintptr_t)a; }
+
+// orb_fast_atan2 (orb_hd.h) with the octant chosen before the division: the same operations on the
+// same operands, so the same bits, but one division and one polynomial where the compiler's
+// if-conversion of the two-branch form evaluates both.
+__device__ __forceinline__ float describe_atan2(float y, float x) {
+    const float k = (float)(180 / 3.14159265358979323846);
+    const float p1 = 0.9997878412794807f * k, p3 = -0.3258083974640975f * k;
+    const float p5 = 0.1555786518463281f * k, p7 = -0.04432655554792128f * k;
+    const float eps = (float)2.220446049250313080847e-16;
+    const float ax = x < 0 ? -x : x, ay = y < 0 ? -y : y;
+    const bool flat = ax >= ay;
+    const float c = (flat ? ay : ax) / ((flat ? ax : ay) + eps), c2 = c * c;
+    const float p = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+    float a = flat ? p : 90.f - p;
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
+    return a;
+}
+
+// The eight 64-lane ballots b[m] to lanes: lane m gets the low half of b[m], lane 32 + m the high half
+// (v_writelane_b32, one instruction per word, in place of a per-lane select chain).  One statement,
+// so that every compare precedes it, and s_nop 1 first: gfx950 wants two wait states between a VALU
+// write of an SGPR (the last v_cmp) and a VALU read of it, which the compiler does not count into
+// inline assembly.
+__device__ __forceinline__ uint32_t ballots_to_lanes(const unsigned long long (&b)[8]) {
+    uint32_t w = 0;
+    asm("s_nop 1\n\t"
+        "v_writelane_b32 %0, %1, 0\n\tv_writelane_b32 %0, %2, 32\n\t"
+        "v_writelane_b32 %0, %3, 1\n\tv_writelane_b32 %0, %4, 33\n\t"
+        "v_writelane_b32 %0, %5, 2\n\tv_writelane_b32 %0, %6, 34\n\t"
+        "v_writelane_b32 %0, %7, 3\n\tv_writelane_b32 %0, %8, 35\n\t"
+        "v_writelane_b32 %0, %9, 4\n\tv_writelane_b32 %0, %10, 36\n\t"
+        "v_writelane_b32 %0, %11, 5\n\tv_writelane_b32 %0, %12, 37\n\t"
+        "v_writelane_b32 %0, %13, 6\n\tv_writelane_b32 %0, %14, 38\n\t"
+        "v_writelane_b32 %0, %15, 7\n\tv_writelane_b32 %0, %16, 39"
+        : "+v"(w)
+        : "s"((uint32_t)b[0]), "s"((uint32_t)(b[0] >> 32)), "s"((uint32_t)b[1]), "s"((uint32_t)(b[1] >> 32)),
+          "s"((uint32_t)b[2]), "s"((uint32_t)(b[2] >> 32)), "s"((uint32_t)b[3]), "s"((uint32_t)(b[3] >> 32)),
+          "s"((uint32_t)b[4]), "s"((uint32_t)(b[4] >> 32)), "s"((uint32_t)b[5]), "s"((uint32_t)(b[5] >> 32)),
+          "s"((uint32_t)b[6]), "s"((uint32_t)(b[6] >> 32)), "s"((uint32_t)b[7]), "s"((uint32_t)(b[7] >> 32)));
+    return w;
+}
+
+// Vertical 7-tap pass at one sample (r, c), |r|, |c| <= 18 from the keypoint, given as the bit
+// patterns rb, cb of r + kRound2 and c + kRound2 (low 24 bits 0x400000 + r: the integer is never
+// extracted).  Blurred row i = r + 18 reads sum rows i .. i+6: the 4 row pairs from i >> 1, which an
+// odd i shifts down by one row (v_alignbit by 16 (i & 1), taken from rb << 4; the half shifted in
+// at the top meets weight 0).  The byte address is 80 (i & ~1) + 4 (c + 18) past the region: a
+// 24-bit multiply-add of rb & ~1 (18 is even) and a shift-add of cb, whose constant parts are folded
+// into `base` (blur_base).  |r|, |c| <= 18 keeps the four words, read as two ds_read2_b32, inside
+// rows 0 .. 43 and columns 0 .. 36 of the region.
+__device__ __forceinline__ uint32_t blur_base(uint32_t region) {
+    return region + 4u * (9u * kHPW + 18u) - 0x400000u * (2u * kHPW) - (kRoundBits << 2);
+}
+__device__ __forceinline__ int blur_sample(uint32_t base, uint32_t rb, uint32_t cb) {
+    uint32_t row = __umul24(rb & ~1u, 2u * kHPW) + base;  // v_mad_u32_u24
+    asm("" : "+v"(row));  // keep the sum as (multiply-add) + (shift-add): two instructions, not three
+    const lds_u32* p = lds_at((cb << 2) + row);
+    const uint32_t s = rb << 4, p0 = p[0], p1 = p[kHPW], p2 = p[2 * kHPW], p3 = p[3 * kHPW];
     uint32_t acc = 1u << 15;
-    acc = __builtin_amdgcn_udot2(as_u16x2(p[0]), odd ? w16(0, 18) : w16(18, 34), acc, false);
-    acc = __builtin_amdgcn_udot2(as_u16x2(p[kHPW]), odd ? w16(34, 48) : w16(48, 56), acc, false);
-    acc = __builtin_amdgcn_udot2(as_u16x2(p[2 * kHPW]), odd ? w16(56, 48) : w16(48, 34), acc, false);
-    acc = __builtin_amdgcn_udot2(as_u16x2(p[3 * kHPW]), odd ? w16(34, 18) : w16(18, 0), acc, false);
+    acc = __builtin_amdgcn_udot2(as_u16x2(__builtin_amdgcn_alignbit(p1, p0, s)), w16(18, 34), acc, false);
+    acc = __builtin_amdgcn_udot2(as_u16x2(__builtin_amdgcn_alignbit(p2, p1, s)), w16(48, 56), acc, false);
+    acc = __builtin_amdgcn_udot2(as_u16x2(__builtin_amdgcn_alignbit(p3, p2, s)), w16(48, 34), acc, false);
+    acc = __builtin_amdgcn_udot2(as_u16x2(__builtin_amdgcn_alignbit(p3, p3, s)), w16(18, 0), acc, false);
     return (int)(acc >> 16);  // <= 255 exactly
 }
 
@@ -2011,9 +2150,11 @@ __global__ __launch_bounds__(256) void k_describe(const KernelGeom* __restrict__
     const int li = hl & 15;
     const int cnt_l = li < g.nlevels ? sel_count[(size_t)f * g.nlevels + li] : 0;
     const int lap_l = li < g.nlevels ? lap_count[(size_t)f * g.nlevels + li] : 0;
-    uint32_t pat[8], exc[kExcPerLane], disc[16];
+    uint32_t pat[8], exc[kExcPerLane], disc[16], hit[kHRounds];
 #pragma unroll
     for (int m = 0; m < 8; ++m) pat[m] = c_pattern_packed.w[32 * m + hl];
+#pragma unroll
+    for (int it = 0; it < kHRounds; ++it) hit[it] = c_hitems.w[it][hl];
 #pragma unroll
     for (int m = 0; m < 16; ++m) disc[m] = c_disc.w[hl][m];
 #pragma unroll
@@ -2097,20 +2238,22 @@ __global__ __launch_bounds__(256) void k_describe(const KernelGeom* __restrict__
     }
     m10 = half_wave_sum(m10);
     m01 = half_wave_sum(m01);
-    const float angle = orb_fast_atan2((float)m01, (float)m10);
+    const float angle = describe_atan2((float)m01, (float)m10);
     // ---- horizontal 7-tap pass (GaussianBlur 7x7 sigma 2, exact in 16 bits): item (pair j, quad qq)
     // = sum columns 4qq .. 4qq+3 of rows 2j, 2j+1 (v_alignbyte + v_dot4_u32_u8 on the patch bytes
-    // shifted by sh), written over the patch in place.  Rounds run from the last pairs down: pair j's
-    // words start at patch row 40j/12, above every row (<= 2j - 1, + 16 over-read bytes) a later,
-    // lower round reads, and within a round the reads precede the writes (one wave, LDS in order).
-    constexpr int kItems = kHP * 10, kIt = (kItems + 31) / 32;
+    // shifted by sh), written over the patch in place.  Only the kHItems items a sample can reach are
+    // computed, lane hl of round `it` taking c_hitems.w[it][hl] (loaded at entry).  The list runs from
+    // the last pairs down: pair j's words start at patch row 40j/12, above the rows of the lower pairs
+    // that later rounds read, and within a round the reads precede the writes (one wave, LDS in
+    // order); hitems_in_place() checks every (earlier write, later read) pair of the list itself.
+    const uint32_t region = lds_addr(P);
 #pragma unroll
-    for (int it = kIt - 1; it >= 0; --it) {
-        const int i = hl + 32 * it, ic = min(i, kItems - 1), j = ic / 10, qq = ic - 10 * j;
+    for (int it = 0; it < kHRounds; ++it) {
+        const lds_u32* src = lds_at(region + (hit[it] & 0xffffu));
         uint32_t o[2][4];
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
-            const uint32_t* w = P + (2 * j + rr) * kPRW + qq;  // patch bytes 4qq .. 4qq+15 (2 x ds_read2)
+            const lds_u32* w = src + rr * kPRW;  // patch bytes 4qq .. 4qq+15 of row 2j + rr (2 x ds_read2)
             const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
             const uint32_t a0 = __builtin_amdgcn_alignbyte(w1, w0, sh);
             const uint32_t a1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
@@ -2124,15 +2267,19 @@ __global__ __launch_bounds__(256) void k_describe(const KernelGeom* __restrict__
             o[rr][3] = __builtin_amdgcn_udot4(a2, kBlurS2[3], __builtin_amdgcn_udot4(a1, kBlurS1[3],
                                               __builtin_amdgcn_udot4(a0, kBlurS0[3], 0u, false), false), false);
         }
-        if (i < kItems)
-            *reinterpret_cast<uint4*>(P + j * kHPW + 4 * qq) =
-                make_uint4(o[0][0] | o[1][0] << 16, o[0][1] | o[1][1] << 16, o[0][2] | o[1][2] << 16, o[0][3] | o[1][3] << 16);
+        // row 2j in the low half, row 2j + 1 in the high half (sums < 2^16): one v_perm per word
+        lds_u32* dstw = lds_at(region + (hit[it] >> 16));
+        uint32_t pk[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pk[k] = __builtin_amdgcn_perm(o[1][k], o[0][k], 0x05040100u);
+        *reinterpret_cast<__attribute__((address_space(3))) v4u32*>(dstw) = v4u32{pk[0], pk[1], pk[2], pk[3]};
     }
     wave_sync();
     // ---- steered BRIEF on the blurred samples (src:150-203)
     const float ang = angle * (float)(3.14159265358979323846 / 180.f);
     float a, b;
     steer_sincos(ang, exc, half, hl, &b, &a);  // a = cos, b = sin
+    const uint32_t bbase = blur_base(region);
     int t0[8], t1[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
@@ -2142,25 +2289,24 @@ __global__ __launch_bounds__(256) void k_describe(const KernelGeom* __restrict__
         const float px1 = (float)((pw4 << 8) >> 24), py1 = (float)(pw4 >> 24);
         // (r, c) = (fma(x, b, y*a), fma(x, a, -(y*b))) as one packed multiply and one packed FMA
         // (y*(-b) == -(y*b) exactly), rounded to nearest-even by adding 1.5 * 2^23 and reading the
-        // integer out of the mantissa (|r|, |c| <= 18)
+        // integer in the mantissa (|r|, |c| <= 18), where blur_sample takes it from
         const f32x2 rc0 = __builtin_elementwise_fma(f32x2{px0, px0}, f32x2{b, a}, f32x2{py0, py0} * f32x2{a, -b}) + kRound2;
         const f32x2 rc1 = __builtin_elementwise_fma(f32x2{px1, px1}, f32x2{b, a}, f32x2{py1, py1} * f32x2{a, -b}) + kRound2;
-        t0[m] = blur_sample(P, __float_as_int(rc0.x) - kRoundBits, __float_as_int(rc0.y) - kRoundBits);
-        t1[m] = blur_sample(P, __float_as_int(rc1.x) - kRoundBits, __float_as_int(rc1.y) - kRoundBits);
+        t0[m] = blur_sample(bbase, __float_as_uint(rc0.x), __float_as_uint(rc0.y));
+        t1[m] = blur_sample(bbase, __float_as_uint(rc1.x), __float_as_uint(rc1.y));
     }
-    uint32_t words[8];
+    // descriptor word m of the half-wave goes to its lane m
+    unsigned long long bal[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) words[m] = (uint32_t)(ballot(t0[m] < t1[m]) >> (32 * (half & 1)));
+    for (int m = 0; m < 8; ++m) bal[m] = ballot(t0[m] < t1[m]);
+    const uint32_t word = ballots_to_lanes(bal);
     if (!active) return;
     const int rk = rk_spec;
     const int dst = rk < 0 ? total - 1 - (lap_before + (-rk - 1)) : mono_before + rk;
     uint8_t* drow = stage_mode == 1 ? st_desc + st_idx * 32 : desc + ((size_t)f * cap + dst) * 32;
     orb_keypoint_t* kdst = stage_mode == 1 ? st_kp + st_idx : kps + (size_t)f * cap + dst;
     if (hl < 8) {
-        uint32_t w = words[0];
-#pragma unroll
-        for (int m = 1; m < 8; ++m) if (hl == m) w = words[m];
-        reinterpret_cast<uint32_t*>(drow)[hl] = w;
+        reinterpret_cast<uint32_t*>(drow)[hl] = word;
     } else if (hl == 8) {
         orb_keypoint_t k;
         float fx = (float)x, fy = (float)y;
