@@ -710,46 +710,50 @@ __global__ __launch_bounds__(256) void k_debug_blur(const uint8_t* __restrict__ 
 // (a candidate survives iff its score beats the 8 neighbours' *thresholded* scores inside the
 // window) is then equivalent to: score >= t && score > score(n) for every neighbour n inside the
 // window's detectable region (neighbours below t can never beat a corner).
-// Packed: the 16 differences d = v - x go into 8 u16 pairs (circle points k, k+8), offset by 256
-// (values 1..511, so unsigned v_pk_min/max_u16 order them), and every sliding min / max step works on
-// both halves at once; wrapping past point 15 is the pair with its halves swapped.
+// Packed: the 16 circle pixels go into 8 u16 pairs (circle points k, k+8) and every v_pk_min/max_u16
+// works on both halves at once; wrapping past point 15 is the pair with its halves swapped.
 __device__ __forceinline__ u16x2 swap16(u16x2 a) { return __builtin_shufflevector(a, a, 1, 0); }
-__device__ __forceinline__ int fast_score(const uint8_t* __restrict__ p, const int (&off)[16]) {
-    const int v = p[0];
-    const u16x2 vv = w16(v + 256, v + 256);
-    u16x2 D[8];
+// q points at the circle's bounding box corner (y-3, x-3) and off[] / ctr are offsets from it: none is
+// negative, so with a compile-time stride all 17 byte reads share one address register (LDS offsets
+// are unsigned immediates; opaque_base keeps the compiler from folding the corner back into them).
+__device__ __forceinline__ int opaque_base(int b) { asm("" : "+v"(b)); return b; }
+__device__ __forceinline__ int fast_score(const uint8_t* __restrict__ q, const int (&off)[16], int ctr) {
+    const int v = q[ctr];
+    // min and max commute with x -> v - x, so the arcs are taken over the circle pixels themselves and v
+    // enters once at the end: score = max(v - min_arcs max_arc x, max_arcs min_arc x - v) - 1
+    u16x2 X[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-        D[k] = vv - __builtin_bit_cast(u16x2, (uint32_t)p[off[k]] | ((uint32_t)p[off[k + 8]] << 16));
-    auto at = [&](const u16x2 (&a)[8], int k) { return k < 8 ? a[k] : swap16(a[k - 8]); };
-    u16x2 mn2[8], mx2[8], mn4[8], mx4[8];
+    for (int k = 0; k < 8; ++k) X[k] = __builtin_bit_cast(u16x2, (uint32_t)q[off[k]] | ((uint32_t)q[off[k + 8]] << 16));
+    // S[k]: pairs k .. 7 (low half points k .. 7, high half k+8 .. 15); P[k]: pairs 0 .. k (low half points
+    // 0 .. k, high half 8 .. k+8).  Arc k = points k .. k+8 = S[k].lo u P[k].hi and arc k+8 = S[k].hi u
+    // P[k].lo: all 16 arcs are min(S[k], swap(P[k])), 22 packed ops per polarity instead of 32.
+    u16x2 smn[8], smx[8], pmn[8], pmx[8];
+    smn[7] = smx[7] = X[7];
+    pmn[0] = pmx[0] = X[0];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        mn2[k] = __builtin_elementwise_min(D[k], at(D, k + 1));
-        mx2[k] = __builtin_elementwise_max(D[k], at(D, k + 1));
+    for (int k = 6; k >= 0; --k) {
+        smn[k] = __builtin_elementwise_min(X[k], smn[k + 1]);
+        smx[k] = __builtin_elementwise_max(X[k], smx[k + 1]);
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        mn4[k] = __builtin_elementwise_min(mn2[k], at(mn2, k + 2));
-        mx4[k] = __builtin_elementwise_max(mx2[k], at(mx2, k + 2));
+    for (int k = 1; k < 8; ++k) {
+        pmn[k] = __builtin_elementwise_min(X[k], pmn[k - 1]);
+        pmx[k] = __builtin_elementwise_max(X[k], pmx[k - 1]);
     }
-    // arc k (points k .. k+8) in the low half, arc k+8 in the high half
-    u16x2 dark = w16(0, 0), bright = w16(0xffff, 0xffff);
+    u16x2 hi = w16(0, 0), lo = w16(0xffff, 0xffff);  // largest arc minimum, smallest arc maximum
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const u16x2 mn8 = __builtin_elementwise_min(mn4[k], at(mn4, k + 4));
-        const u16x2 mx8 = __builtin_elementwise_max(mx4[k], at(mx4, k + 4));
-        dark = __builtin_elementwise_max(dark, __builtin_elementwise_min(mn8, swap16(D[k])));
-        bright = __builtin_elementwise_min(bright, __builtin_elementwise_max(mx8, swap16(D[k])));
+        hi = __builtin_elementwise_max(hi, __builtin_elementwise_min(smn[k], swap16(pmn[k])));
+        lo = __builtin_elementwise_min(lo, __builtin_elementwise_max(smx[k], swap16(pmx[k])));
     }
-    const int best_dark = (int)max(dark.x, dark.y) - 256, best_bright = (int)min(bright.x, bright.y) - 256;
-    return max(best_dark, -best_bright) - 1;
+    const int best_dark = v - (int)min(lo.x, lo.y), best_bright = (int)max(hi.x, hi.y) - v;
+    return max(best_dark, best_bright) - 1;
 }
 
 __device__ __forceinline__ bool is_local_max(const uint8_t* __restrict__ sc, int stride, int idx, int s) {
-    const uint8_t* q = sc + idx;
-    return s > q[-stride - 1] && s > q[-stride] && s > q[-stride + 1] && s > q[-1] && s > q[1] &&
-           s > q[stride - 1] && s > q[stride] && s > q[stride + 1];
+    const uint8_t* q = sc + opaque_base(idx - stride - 1);  // the ring's corner: no negative offset
+    return s > q[0] && s > q[1] && s > q[2] && s > q[stride] && s > q[stride + 2] &&
+           s > q[2 * stride] && s > q[2 * stride + 1] && s > q[2 * stride + 2];
 }
 
 __device__ __forceinline__ uint32_t pack_key(int x, int y, int score) {
@@ -823,7 +827,7 @@ __device__ __forceinline__ void fast_cell(const KernelGeom& g, const CellDesc& C
         const int cx[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
         const int cy[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
 #pragma unroll
-        for (int k = 0; k < 16; ++k) off[k] = cx[k] + cy[k] * ws;
+        for (int k = 0; k < 16; ++k) off[k] = cx[k] + 3 + (cy[k] + 3) * ws;  // from (y-3, x-3), see fast_score
     }
     const int ini = g.ini_th, mint = g.min_th;
     // 1. compass filter at iniTh and minTh in one pass: a 9-pixel arc always contains two circle
@@ -944,7 +948,7 @@ __device__ __forceinline__ void fast_cell(const KernelGeom& g, const CellDesc& C
             int idx = 0, s = -1;
             if (j < nlist) {
                 idx = cl[j];
-                s = fast_score(win + (idx >> 7) * ws + (idx & 127), off);
+                s = fast_score(win + opaque_base(((idx >> 7) - 3) * ws + (idx & 127) - 3), off, 3 * ws + 3);
             }
             const bool is_c = s >= t;
             const unsigned long long m = ballot(is_c);
@@ -1018,7 +1022,8 @@ __global__ __launch_bounds__(256) void k_fast_cells(const KernelGeom* __restrict
                                                     int groups, int nblocks, int share) {
     const KernelGeom& g = *gp;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // (the wave index made wave-uniform: the cell record and everything derived from it stay in SGPRs)
+    const int wave = uniform(threadIdx.x >> 6), lane = threadIdx.x & 63;
     // XCD-chunked block order (xcd_tile): neighbouring cells, whose windows overlap, share an L2 (the
     // pyramid's frame-affine order measured no fetch change here: the windows miss L2 either way)
     const int tb = xcd_tile(blockIdx.x, share);
