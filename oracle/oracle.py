@@ -40,6 +40,8 @@ _PROTOS = {
     "oracle_hamming_knn2": (None, [_vp, _i, _vp, _i, _vp, _vp, _vp]),
     "oracle_search_for_triangulation": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "oracle_local_ba": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "oracle_local_ba_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(_i)]),
+    "oracle_local_ba_contracted_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(_i)]),
     "oracle_search_by_projection_frame": (_i, [_vp, _vp, _f, _i, _i, _vp]),
     "oracle_search_by_projection_local": (_i, [_vp, _vp, _vp, _f, _i, _f, _f, _vp]),
     "oracle_pose_optimization": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
@@ -241,10 +243,21 @@ class _BaResult(ctypes.Structure):
                 ("lambda_", ctypes.c_double)]
 
 
-def local_ba(prob: dict, iterations: int = 10, user_lambda_init: float = 0.0, stop_flag=None):
+BA_TRACE_DTYPE = np.dtype([(k, "<f8") for k in ("iteration", "qmax", "lambda", "current_chi", "temp_chi", "scale",
+                                                 "rho", "solve_ok", "accepted")])
+
+
+def local_ba(prob: dict, iterations: int = 10, user_lambda_init: float = 0.0, stop_flag=None, trace: bool = False,
+             contracted: bool = False):
     """Oracle g2o LM/Schur solve of a flattened LocalBundleAdjustment graph (see oracle/orb_ba_oracle.cpp).
     prob: dict of arrays (pose [n,7] t+q, pose_id, pose_fixed, pose_camera (5 x f4 records), point [m,3],
-    point_id, edges (40-byte records)).  Returns (pose, point, edge_chi2, depth_ok, result dict)."""
+    point_id, edges (40-byte records)).  Returns (pose, point, edge_chi2, depth_ok, result dict).
+    trace=True appends a sixth value: one BA_TRACE_DTYPE record per LM trial (the iteration, qmax and lambda
+    the trial started with, currentChi, tempChi, computeScale's value, rho, whether the linear solve
+    succeeded and whether the trial was accepted).  contracted=True (with trace=True) runs the build of the
+    same code whose products and sums contract into fused multiply-adds (oracle/orb_ba_oracle_contracted.cpp):
+    a second rounding of the reference, for judging a problem's conditioning."""
+    assert trace or not contracted
     pose = np.ascontiguousarray(prob["pose"], dtype=np.float64).copy()
     point = np.ascontiguousarray(prob["point"], dtype=np.float64).copy()
     pid = np.ascontiguousarray(prob["pose_id"], dtype=np.int64)
@@ -260,9 +273,20 @@ def local_ba(prob: dict, iterations: int = 10, user_lambda_init: float = 0.0, st
     chi2 = np.zeros(len(edges))
     depth = np.zeros(len(edges), np.uint8)
     r = _BaResult()
-    load().oracle_local_ba(ctypes.byref(s), ctypes.byref(o), chi2.ctypes.data, depth.ctypes.data, ctypes.byref(r))
+    if trace:
+        cap = 10 * max(int(iterations), 0) + 1  # at most 10 trials per iteration
+        rec = np.zeros(cap, BA_TRACE_DTYPE)
+        nrec = ctypes.c_int(0)
+        fn = load().oracle_local_ba_contracted_trace if contracted else load().oracle_local_ba_trace
+        fn(ctypes.byref(s), ctypes.byref(o), chi2.ctypes.data, depth.ctypes.data,
+                                     ctypes.byref(r), rec.ctypes.data, cap, ctypes.byref(nrec))
+        assert nrec.value <= cap
+    else:
+        load().oracle_local_ba(ctypes.byref(s), ctypes.byref(o), chi2.ctypes.data, depth.ctypes.data, ctypes.byref(r))
     res = {"iterations": r.iterations, "trials": r.trials, "terminated": r.terminated, "stopped": r.stopped,
            "initial_chi2": r.initial_chi2, "final_chi2": r.final_chi2, "lambda": r.lambda_}
+    if trace:
+        return pose, point, chi2, depth.astype(bool), res, rec[:nrec.value].copy()
     return pose, point, chi2, depth.astype(bool), res
 
 

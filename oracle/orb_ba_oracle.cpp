@@ -135,10 +135,15 @@ void linearize(const Problem& P, int e, double A[9], double B[18]) {
 
 }  // namespace
 
+#define ORACLE_BA_TRACE_FIELDS 9
+
 namespace {
 // Test hook (oracle_local_ba_stop_after): the solve behaves as if the caller's stop flag went up right
 // after trial `stop_after_trials` (0: before the first iteration).
 int g_stop_after = -1;
+// Trace hook (oracle_local_ba_trace): one record of ORACLE_BA_TRACE_FIELDS doubles per LM trial.
+double* g_trace = nullptr;
+int g_trace_cap = 0, g_trace_n = 0;
 }  // namespace
 
 extern "C" int oracle_local_ba(orb_ba_problem_t* prob, const orb_ba_options_t* opt, double* edge_chi2_out,
@@ -275,6 +280,7 @@ extern "C" int oracle_local_ba(orb_ba_problem_t* prob, const orb_ba_options_t* o
         do {
             pose_bak = P.pose;  // push
             point_bak = P.point;
+            const double lambda_before = lambda, chi_before = currentChi;
             // ---- setLambda + Schur complement (BlockSolver::solve)
             std::fill(S.begin(), S.end(), 0.0);
             for (int i = 0; i < P.n_free; ++i)
@@ -346,6 +352,14 @@ extern "C" int oracle_local_ba(orb_ba_problem_t* prob, const orb_ba_options_t* o
             for (int j = 0; j < n + m; ++j) scale += x[j] * (lambda * x[j] + b[j]);
             scale += 1e-3;
             rho /= scale;
+            if (g_trace) {  // iteration, qmax, lambda, currentChi, tempChi, scale, rho, solve ok, accepted
+                if (g_trace_n < g_trace_cap) {
+                    double* t = g_trace + (size_t)ORACLE_BA_TRACE_FIELDS * g_trace_n;
+                    t[0] = it; t[1] = qmax; t[2] = lambda_before; t[3] = chi_before; t[4] = tempChi;
+                    t[5] = scale; t[6] = rho; t[7] = ok2 ? 1 : 0; t[8] = (rho > 0 && std::isfinite(tempChi)) ? 1 : 0;
+                }
+                g_trace_n++;
+            }
             if (rho > 0 && std::isfinite(tempChi)) {
                 double alpha = 1. - std::pow((2 * rho - 1), 3);
                 alpha = std::min(alpha, 2. / 3.);
@@ -396,5 +410,22 @@ extern "C" int oracle_local_ba_stop_after(orb_ba_problem_t* prob, const orb_ba_o
     g_stop_after = stop_after_trials;
     const int rc = oracle_local_ba(prob, opt, edge_chi2_out, depth_ok_out, res);
     g_stop_after = -1;
+    return rc;
+}
+
+// oracle_local_ba that also records every LM trial: `trace` takes up to `cap` records of
+// ORACLE_BA_TRACE_FIELDS doubles (iteration, qmax before the trial, lambda before the trial, currentChi,
+// tempChi, scale, rho, 1 when the linear solve succeeded, 1 when the trial was accepted); *n_trace is the
+// number of trials run (records beyond `cap` are dropped).  The solve itself is oracle_local_ba's.
+extern "C" int oracle_local_ba_trace(orb_ba_problem_t* prob, const orb_ba_options_t* opt, double* edge_chi2_out,
+                                     uint8_t* depth_ok_out, orb_ba_result_t* res, double* trace, int cap,
+                                     int* n_trace) {
+    g_trace = trace;
+    g_trace_cap = cap;
+    g_trace_n = 0;
+    const int rc = oracle_local_ba(prob, opt, edge_chi2_out, depth_ok_out, res);
+    if (n_trace) *n_trace = g_trace_n;
+    g_trace = nullptr;
+    g_trace_cap = 0;
     return rc;
 }

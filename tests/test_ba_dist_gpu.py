@@ -34,9 +34,14 @@ def _worker(rank, world, port, kw, q):
         from conftest import load_package
         pkg = load_package()
         from orbslam3_amd import synth
-        prob = synth.local_ba_problem(**kw)
+        if isinstance(kw, str):  # the name of a case of ba_cases.py
+            import ba_cases
+            case = ba_cases.get(kw)
+            prob, args = ba_cases.build(case), (case.iterations, case.user_lambda_init)
+        else:
+            prob, args = synth.local_ba_problem(**kw), (10,)
         ba = pkg.LocalBA().attach(transport="host")
-        pose, point, chi2, depth, res = ba.optimize(prob, 10)
+        pose, point, chi2, depth, res = ba.optimize(prob, *args)
         q.put((rank, (pose, point, chi2, depth, res)))
     except Exception as e:  # noqa: BLE001
         q.put((rank, repr(e)))
@@ -99,6 +104,23 @@ def test_sharded_local_ba_matches_oracle(oracle, synth, world, stereo_frac, seed
         # every rank holds the same result
         assert np.array_equal(pose, out[0][0]) and np.array_equal(point, out[0][1])
         assert np.array_equal(chi2, out[0][2])
+
+
+def test_sharded_local_ba_rejecting_case(oracle):
+    """Two ranks on a case whose LM loop rejects 14 of its 24 trials (ba_cases.SHARDED_CASE): every rank takes
+    the oracle's path -- so the same rejects -- and holds the same bytes, at the bars of test_ba_cases_gpu.py."""
+    import ba_cases
+    case = ba_cases.get(ba_cases.SHARDED_CASE)
+    assert case.path.count("R") >= 2 and "RR" in case.path
+    out = _run(2, case.name)
+    prob = ba_cases.build(case)
+    ref = ba_cases.solve_oracle(oracle, case, prob)
+    assert ba_cases.path_string(ref[5]) == case.path
+    for r in range(2):
+        ba_cases.assert_matches_oracle(case, prob, out[r], ref, tag=f"rank {r}: ")
+        for a, b in zip(out[r][:4], out[0][:4]):
+            assert np.array_equal(a, b)
+        assert out[r][4] == out[0][4]
 
 
 def _rccl_one_rank_worker(port, kw, q):
