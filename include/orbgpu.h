@@ -997,6 +997,56 @@ int orb_track_reference_kf_device(orb_matcher_t m, const orb_kf_device_t* kf, co
                                   const orb_frame_device_t* frame, const float* inv_level_sigma2, const double pose7[7],
                                   int imu, const orb_track_reference_kf_buffers_t* bufs, void* stream);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc; the loop / merge candidates of src/LoopClosing.cc:899-913) ----------
+ * The RANSAC of Sim3Solver::iterate for n_problems candidates in one call: every hypothesis of every
+ * problem is evaluated (ComputeSim3 + CheckInliers, :311-439) and the reference's serial control flow is a
+ * selection over the counts.  Pinhole cameras only (fx * x / z + cx), like the rest of the library.
+ *
+ * One problem is what the Sim3Solver constructor gathers (:71-118): the camera-frame points mvX3Dc1 /
+ * mvX3Dc2, the thresholds mvnMaxError1 / 2 = (float)(9.210 * sigma2) and the two cameras; the library
+ * computes mvP1im1 / mvP2im2 itself.  The sample triples are an input: the reference draws them with
+ * DUtils::Random::RandomInt, and that generator and its state belong to the caller (row h: the three
+ * indices of iteration h, in draw order).
+ *
+ * Per hypothesis: Horn's closed form in FP64 on the float32 points, T12 and T21 rounded to float32 once;
+ * the reprojections in float32 without contraction; inlier = err1 < max_err1[i] && err2 < max_err2[i], no
+ * depth gate.  A hypothesis whose transform is not finite (|v| = 0: the two triples differ by a
+ * translation) scores 0.  n < min_inliers (the reference's bNoMore on entry): nothing is evaluated, winner =
+ * best = -1, inlier_mask zero, the per-hypothesis arrays are not written. */
+typedef struct orb_sim3_problem {
+    int32_t n;               /* correspondences, 0 .. 2^20 */
+    const float* x3dc1;      /* n x 3: mvX3Dc1 */
+    const float* x3dc2;      /* n x 3: mvX3Dc2 */
+    const float* max_err1;   /* n: mvnMaxError1 */
+    const float* max_err2;   /* n: mvnMaxError2 */
+    float cam1[4], cam2[4];  /* fx, fy, cx, cy of pKF1's and pKF2's pinhole camera */
+    int32_t fix_scale;       /* mbFixScale */
+    int32_t min_inliers;     /* mRansacMinInliers */
+    int32_t n_hyp;           /* mRansacMaxIts, 1 .. 1024 */
+    const int32_t* samples;  /* n_hyp x 3 indices into 0 .. n-1, the three of a row distinct */
+} orb_sim3_problem_t;
+
+typedef struct orb_sim3_out {
+    int32_t* hyp_inliers;    /* n_hyp: mnInliersi of every hypothesis (-1: invalid triple, device form only) */
+    float* hyp_t12;          /* n_hyp x 12: mT12i's rows [s R | t] */
+    float* hyp_scale;        /* n_hyp: ms12i */
+    int32_t* winner;         /* 1: the first hypothesis with hyp_inliers > min_inliers, or -1 */
+    int32_t* best;           /* 1: the last hypothesis attaining the maximum count (the reference updates its
+                                best on >=), or -1 when nothing was evaluated */
+    uint8_t* inlier_mask;    /* n: mvbInliersi of winner if there is one, else of best */
+    uint64_t* hyp_mask;      /* n_hyp x ceil(n / 64) words, bit i & 63 of word i >> 6 = point i: every
+                                hypothesis's inliers; NULL (production callers): not reported */
+} orb_sim3_out_t;
+
+/* Host pointers.  Every triple is checked: an index outside 0 .. n-1 or repeated in its row is ORB_ERR_ARG.
+ * n_problems == 0: ORB_OK, nothing launched. */
+int orb_sim3_ransac(const orb_sim3_problem_t* problems, int n_problems, const orb_sim3_out_t* outs);
+/* Device pointers inside the (host) problem and output records, no host hop, asynchronous on `stream`.
+ * The triples cannot be checked here: a row with an index out of range or repeated is not read, its
+ * hypothesis reports hyp_inliers -1 and a NaN transform, and it is never selected. */
+int orb_sim3_ransac_device(const orb_sim3_problem_t* problems, int n_problems, const orb_sim3_out_t* outs,
+                           void* stream);
+
 /* ---- multi-GPU local BA: one process per GPU, every rank passes the same
  * problem; rank r owns a contiguous, edge-balanced range of the landmarks and their edges, and
  * the ranks all-reduce the partial Hpp/b_p, the partial reduced camera system (S, b_S) of each LM

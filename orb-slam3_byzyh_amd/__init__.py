@@ -11,9 +11,10 @@ from .keyframe import DeviceKeyFrame, Frame, FusePoints, KeyFrame, LocalMapPoint
 from .matcher import ORBmatcher
 from .optimizer import LocalBA, local_bundle_adjustment, pose_optimization
 from . import distributed, timers
+from .sim3 import Sim3Problem, Sim3Solver, draw_samples, ransac_max_its
 from .stereo import compute_stereo_matches, compute_stereo_matches_batch_device
 from .tracking import (DeviceFrame, DeviceLastPoints, DeviceLocalMap, TrackingChain, TrackingChainBatch,
                        TrackReferenceKeyFrame)
 from .vocabulary import ORBVocabulary
 
-__all__ = ["ORBextractor", "ORBmatcher", "KeyFrame", "Frame", "FusePoints", "LocalMapPoints", "LocalBA", "local_bundle_adjustment", "pose_optimization", "compute_stereo_matches", "compute_stereo_matches_batch_device", "ORBVocabulary", "frustum_frame", "is_in_frustum", "KEYPOINT_DTYPE", "OrbGpuError", "keypoints_to_structured", "undistort_keypoints_device", "DeviceFrame", "DeviceLastPoints", "DeviceLocalMap", "TrackingChain", "TrackingChainBatch", "TrackReferenceKeyFrame", "_lib"]
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrame", "Frame", "FusePoints", "LocalMapPoints", "LocalBA", "local_bundle_adjustment", "pose_optimization", "compute_stereo_matches", "compute_stereo_matches_batch_device", "ORBVocabulary", "frustum_frame", "is_in_frustum", "KEYPOINT_DTYPE", "OrbGpuError", "keypoints_to_structured", "undistort_keypoints_device", "DeviceFrame", "DeviceLastPoints", "DeviceLocalMap", "TrackingChain", "TrackingChainBatch", "TrackReferenceKeyFrame", "Sim3Problem", "Sim3Solver", "draw_samples", "ransac_max_its", "_lib"]

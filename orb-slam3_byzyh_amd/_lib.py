@@ -57,6 +57,19 @@ def vocabulary_view(voc: dict) -> tuple:
     return v, arrs
 
 
+class Sim3Problem(ctypes.Structure):  # orb_sim3_problem_t
+    _fields_ = [("n", ctypes.c_int32), ("x3dc1", ctypes.c_void_p), ("x3dc2", ctypes.c_void_p),
+                ("max_err1", ctypes.c_void_p), ("max_err2", ctypes.c_void_p), ("cam1", ctypes.c_float * 4),
+                ("cam2", ctypes.c_float * 4), ("fix_scale", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("n_hyp", ctypes.c_int32), ("samples", ctypes.c_void_p)]
+
+
+class Sim3Out(ctypes.Structure):  # orb_sim3_out_t
+    _fields_ = [("hyp_inliers", ctypes.c_void_p), ("hyp_t12", ctypes.c_void_p), ("hyp_scale", ctypes.c_void_p),
+                ("winner", ctypes.c_void_p), ("best", ctypes.c_void_p), ("inlier_mask", ctypes.c_void_p),
+                ("hyp_mask", ctypes.c_void_p)]
+
+
 class OrbGpuError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str = ""):
         super().__init__(f"{where} failed with status {code}: {msg}")
@@ -136,6 +149,8 @@ PROTOTYPES = {
                                         _vp]),
     "orb_track_reference_kf_scratch_bytes": (_sz, [_i]),
     "orb_track_reference_kf_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "orb_sim3_ransac": (_i, [_vp, _i, _vp]),
+    "orb_sim3_ransac_device": (_i, [_vp, _i, _vp, _vp]),
     "orb_ba_create": (_i, [ctypes.POINTER(_vp)]),
     "orb_ba_destroy": (_i, [_vp]),
     "orb_ba_optimize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
