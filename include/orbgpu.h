@@ -1047,6 +1047,50 @@ int orb_sim3_ransac(const orb_sim3_problem_t* problems, int n_problems, const or
 int orb_sim3_ransac_device(const orb_sim3_problem_t* problems, int n_problems, const orb_sim3_out_t* outs,
                            void* stream);
 
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:4195-4494; called per loop / merge candidate at
+ * src/LoopClosing.cc:689 and :991) ------------------------------------------------------------------------
+ * The Levenberg-Marquardt refinement of S12 on one 7-DoF vertex with two reprojection edges per matched pair
+ * (e12 = obs1 - project1(S12 P2c), e21 = obs2 - project2(S12^-1 P1c)), for n_problems candidates in one
+ * call, FP64.  The whole schedule runs on the device: optimize(5) with Huber sqrt(th2), the first cull on the
+ * stored errors (those of the last state the solver evaluated), the early return when fewer than 10 pairs are
+ * left, optimize(10 or 5) without kernels, the second cull at the final estimate.  The edges are
+ * differentiated numerically as g2o does (central differences, delta 1e-9).  Pinhole cameras only.
+ *
+ * One problem is the gathered graph (:4254-4407), one entry per pair that got its two edges, in gather order.
+ * At most ORB_OPTSIM3_MAX_PAIRS pairs: the pairs live in the workgroup's LDS (88 bytes each); a larger n is
+ * ORB_ERR_ARG. */
+#define ORB_OPTSIM3_MAX_PAIRS 1024
+typedef struct orb_optsim3_problem {
+    int32_t n;                   /* nCorrespondences, 0 .. ORB_OPTSIM3_MAX_PAIRS */
+    const double* p1c;           /* n x 3: P3D1c (float32 R1w X + t1w, cast to double) */
+    const double* p2c;           /* n x 3: P3D2c */
+    const double* obs1;          /* n x 2: mvKeysUn[i].pt of KF1 */
+    const double* obs2;          /* n x 2: mvKeysUn[i2].pt of KF2, or the normalised (x / z, y / z) when i2 < 0 */
+    const float* inv_sigma2_1;   /* n: information of e12 */
+    const float* inv_sigma2_2;   /* n: information of e21 */
+    float cam1[4], cam2[4];      /* fx, fy, cx, cy of pKF1's and pKF2's pinhole camera */
+    double s12[8];               /* g2oS12 in g2o::Sim3::operator[] order: qx qy qz qw tx ty tz s */
+    float th2;                   /* > 0 */
+    int32_t fix_scale;           /* bFixScale */
+} orb_optsim3_problem_t;
+
+typedef struct orb_optsim3_out {
+    double* s12_out;   /* 8: the refined g2oS12; the input when the call returns through the < 10 exit */
+    int32_t* n_in;     /* 1: the reference's return value */
+    int32_t* n_bad;    /* 1: nBad of the first cull */
+    uint8_t* inlier;   /* n: 1 exactly where the reference leaves vpMatches1 set (NULL allowed when n == 0) */
+    double* chi2_12;   /* n: each pair's last e12->chi2(): at the final estimate for the pairs that passed the
+                          first cull, else as the first cull saw it; NULL: not reported */
+    double* chi2_21;   /* n: the same for e21; NULL: not reported */
+} orb_optsim3_out_t;
+
+/* Host pointers, synchronous.  Arguments are checked before anything is touched.  n_problems == 0: ORB_OK,
+ * nothing launched.  n == 0: n_in = n_bad = 0, s12_out = s12. */
+int orb_optimize_sim3(const orb_optsim3_problem_t* problems, int n_problems, const orb_optsim3_out_t* outs);
+/* Device pointers inside the (host) problem and output records, no host hop, asynchronous on `stream`. */
+int orb_optimize_sim3_device(const orb_optsim3_problem_t* problems, int n_problems, const orb_optsim3_out_t* outs,
+                             void* stream);
+
 /* ---- multi-GPU local BA: one process per GPU, every rank passes the same
  * problem; rank r owns a contiguous, edge-balanced range of the landmarks and their edges, and
  * the ranks all-reduce the partial Hpp/b_p, the partial reduced camera system (S, b_S) of each LM

@@ -63,6 +63,7 @@
 #include <vector>
 
 #include "orbgpu.h"
+#include "orbgpu_status.hpp"
 
 namespace orbgpu {
 
@@ -324,6 +325,181 @@ int LocalBundleAdjustment(orb_ba_t h, typename A::KeyFrame* pKF, bool* pbStopFla
     return rc;
 }
 
+/* ---- Optimizer::OptimizeSim3 (include/Optimizer.h, src/Optimizer.cc:4195-4494) over orb_optimize_sim3 --------
+ * The gather (:4254-4407) and the write-back of vpMatches1 / g2oS12 stay on the host, restated here over an
+ * access policy of their own; the two optimize() calls and both culls run on the GPU.
+ *
+ *   struct S {
+ *     using KeyFrame = ...; using MapPoint = ...;
+ *     using Sim3 = ...;      // g2o::Sim3
+ *     using Matrix7d = ...;  // Eigen::Matrix<double, 7, 7>
+ *     static std::vector<MapPoint*> MapPointMatches(KeyFrame*);            // GetMapPointMatches()
+ *     static bool IsBad(MapPoint*);
+ *     static int IndexInKeyFrame(MapPoint*, KeyFrame*);                    // get<0>(GetIndexInKeyFrame(pKF))
+ *     static void Pose(KeyFrame*, float Rcw[9], float tcw[3]);             // GetRotation(), GetTranslation()
+ *     static void WorldPos(MapPoint*, float X[3]);
+ *     static void KeyUn(KeyFrame*, int idx, float* x, float* y, int* octave);   // mvKeysUn[idx]
+ *     static float InvLevelSigma2(KeyFrame*, int octave);                  // mvInvLevelSigma2[octave]
+ *     static void Pinhole(KeyFrame*, float K[4]);                          // fx, fy, cx, cy of mpCamera
+ *     static void GetSim3(const Sim3&, double v[8]);                       // operator[] order: q (x y z w), t, s
+ *     static void SetSim3(Sim3&, const double v[8]);
+ *     static void SetZero(Matrix7d&);
+ *   };
+ *
+ * The reference's i2 < 0 rule is kept as it is (:4371-4386): such a pair's obs2 is the NORMALISED float32
+ * (x / z, y / z) of P3D2c, not pixels, and its key point is built without an octave, so the information is
+ * mvInvLevelSigma2[0].  Pinhole cameras only.
+ *
+ * Failures: nothing here throws.  When the library call fails (ORB_ERR_*: a device error, more than
+ * ORB_OPTSIM3_MAX_PAIRS gathered pairs), vpMatches1, g2oS12 and mAcumHessian are left as they were, 0 is returned
+ * and orbgpu::LastShimError() reports the code. */
+template <class S>
+struct OptimizeSim3Candidate {
+    typename S::KeyFrame* pKF1 = nullptr;
+    typename S::KeyFrame* pKF2 = nullptr;
+    std::vector<typename S::MapPoint*>* vpMatches1 = nullptr;
+    typename S::Sim3* g2oS12 = nullptr;
+    float th2 = 10.f;
+    bool bFixScale = true;
+    typename S::Matrix7d* mAcumHessian = nullptr;
+    bool bAllPoints = false;
+    int result = 0;  // OptimizeSim3's return value, set by OptimizeSim3Batch
+
+    // the gathered graph: one entry per pair that got its two edges, in gather order
+    std::vector<double> p1c, p2c, obs1, obs2;
+    std::vector<float> inv_sigma2_1, inv_sigma2_2;
+    std::vector<size_t> vnIndexEdge;
+    float cam1[4], cam2[4];
+    double s12_in[8], s12_out[8];
+    int32_t n_in = 0, n_bad = 0;
+    std::vector<uint8_t> inlier;
+
+    // Rcw * X + tcw as Eigen's fixed-size product evaluates it: each row's three products summed in order
+    static void ToCamera(const float R[9], const float t[3], const float X[3], float out[3]) {
+        for (int r = 0; r < 3; ++r) out[r] = ((R[3 * r] * X[0] + R[3 * r + 1] * X[1]) + R[3 * r + 2] * X[2]) + t[r];
+    }
+
+    void Gather() {
+        p1c.clear(); p2c.clear(); obs1.clear(); obs2.clear();
+        inv_sigma2_1.clear(); inv_sigma2_2.clear(); vnIndexEdge.clear();
+        float R1w[9], t1w[3], R2w[9], t2w[3];
+        S::Pose(pKF1, R1w, t1w);
+        S::Pose(pKF2, R2w, t2w);
+        S::Pinhole(pKF1, cam1);
+        S::Pinhole(pKF2, cam2);
+        S::GetSim3(*g2oS12, s12_in);
+        const int N = (int)vpMatches1->size();
+        const std::vector<typename S::MapPoint*> vpMapPoints1 = S::MapPointMatches(pKF1);
+        for (int i = 0; i < N; ++i) {
+            typename S::MapPoint* pMP2 = (*vpMatches1)[i];
+            if (!pMP2) continue;
+            typename S::MapPoint* pMP1 = vpMapPoints1[i];
+            const int i2 = S::IndexInKeyFrame(pMP2, pKF2);
+            if (!pMP1) continue;  // (the reference adds vPoint2 alone here: a vertex without an edge)
+            if (S::IsBad(pMP1) || S::IsBad(pMP2)) continue;
+            float X[3], P3D1c[3], P3D2c[3];
+            S::WorldPos(pMP1, X);
+            ToCamera(R1w, t1w, X, P3D1c);
+            S::WorldPos(pMP2, X);
+            ToCamera(R2w, t2w, X, P3D2c);
+            if (i2 < 0 && !bAllPoints) continue;
+            if (P3D2c[2] < 0) continue;
+            float x, y;
+            int octave;
+            S::KeyUn(pKF1, i, &x, &y, &octave);
+            obs1.push_back((double)x);
+            obs1.push_back((double)y);
+            inv_sigma2_1.push_back(S::InvLevelSigma2(pKF1, octave));
+            if (i2 >= 0) {
+                S::KeyUn(pKF2, i2, &x, &y, &octave);
+            } else {  // the normalised point, octave 0 (cv::KeyPoint(Point2f, size))
+                const float invz = 1 / P3D2c[2];
+                x = P3D2c[0] * invz;
+                y = P3D2c[1] * invz;
+                octave = 0;
+            }
+            obs2.push_back((double)x);
+            obs2.push_back((double)y);
+            inv_sigma2_2.push_back(S::InvLevelSigma2(pKF2, octave));
+            for (int k = 0; k < 3; ++k) {
+                p1c.push_back((double)P3D1c[k]);
+                p2c.push_back((double)P3D2c[k]);
+            }
+            vnIndexEdge.push_back((size_t)i);
+        }
+        inlier.assign(vnIndexEdge.size(), 0);
+    }
+
+    void Describe(orb_optsim3_problem_t* p, orb_optsim3_out_t* o) {
+        p->n = (int32_t)vnIndexEdge.size();
+        p->p1c = p1c.data(); p->p2c = p2c.data(); p->obs1 = obs1.data(); p->obs2 = obs2.data();
+        p->inv_sigma2_1 = inv_sigma2_1.data(); p->inv_sigma2_2 = inv_sigma2_2.data();
+        for (int k = 0; k < 4; ++k) {
+            p->cam1[k] = cam1[k];
+            p->cam2[k] = cam2[k];
+        }
+        for (int k = 0; k < 8; ++k) p->s12[k] = s12_in[k];
+        p->th2 = th2;
+        p->fix_scale = bFixScale ? 1 : 0;
+        o->s12_out = s12_out; o->n_in = &n_in; o->n_bad = &n_bad;
+        o->inlier = inlier.data();  // (NULL for an empty graph, as the ABI allows)
+        o->chi2_12 = nullptr; o->chi2_21 = nullptr;
+    }
+
+    // vpMatches1 loses the culled pairs (both culls); past the < 10 exit mAcumHessian is zeroed and g2oS12 set
+    void WriteBack() {
+        const int n = (int)vnIndexEdge.size();
+        for (int k = 0; k < n; ++k)
+            if (!inlier[k]) (*vpMatches1)[vnIndexEdge[k]] = nullptr;
+        result = 0;
+        if (n - n_bad < 10) return;
+        S::SetZero(*mAcumHessian);
+        S::SetSim3(*g2oS12, s12_out);
+        result = n_in;
+    }
+};
+
+// Several candidates of one keyframe (the loops of LoopClosing::DetectCommonRegionsFromBoW) in ONE library call.
+// Each candidate's `result` is what OptimizeSim3 returns for it.  On a library failure every candidate keeps its
+// arguments and gets result 0.
+template <class S>
+void OptimizeSim3Batch(std::vector<OptimizeSim3Candidate<S>>& cands) noexcept {
+    try {
+        if (cands.empty()) return;
+        std::vector<orb_optsim3_problem_t> probs(cands.size());
+        std::vector<orb_optsim3_out_t> outs(cands.size());
+        for (size_t k = 0; k < cands.size(); ++k) {
+            cands[k].result = 0;
+            cands[k].Gather();
+            cands[k].Describe(&probs[k], &outs[k]);
+        }
+        if (detail::Failed(orb_optimize_sim3(probs.data(), (int)cands.size(), outs.data()), "orb_optimize_sim3")) return;
+        for (auto& c : cands) c.WriteBack();
+    } catch (...) {  // an allocation failure in the gather: reported like a library failure
+        detail::last_code() = ORB_ERR_INTERNAL;
+        detail::failure_count().fetch_add(1, std::memory_order_relaxed);
+        for (auto& c : cands) c.result = 0;
+    }
+}
+
+// Optimizer::OptimizeSim3's signature and return value.
+template <class S>
+int OptimizeSim3(typename S::KeyFrame* pKF1, typename S::KeyFrame* pKF2, std::vector<typename S::MapPoint*>& vpMatches1,
+                 typename S::Sim3& g2oS12, const float th2, const bool bFixScale, typename S::Matrix7d& mAcumHessian,
+                 const bool bAllPoints = false) noexcept {
+    try {
+        std::vector<OptimizeSim3Candidate<S>> one(1);
+        one[0].pKF1 = pKF1; one[0].pKF2 = pKF2; one[0].vpMatches1 = &vpMatches1; one[0].g2oS12 = &g2oS12;
+        one[0].th2 = th2; one[0].bFixScale = bFixScale; one[0].mAcumHessian = &mAcumHessian; one[0].bAllPoints = bAllPoints;
+        OptimizeSim3Batch<S>(one);
+        return one[0].result;
+    } catch (...) {
+        detail::last_code() = ORB_ERR_INTERNAL;
+        detail::failure_count().fetch_add(1, std::memory_order_relaxed);
+        return 0;
+    }
+}
+
 }  // namespace orbgpu
 
 // ---- the reference's own types (compile inside the ORB-SLAM3 build: define ORBGPU_WITH_ORBSLAM3 and
@@ -387,6 +563,43 @@ struct ORBSLAM3Access {
         p->UpdateNormalAndDepth();
     }
     static void IncreaseChangeIndex(Map* m) { m->IncreaseChangeIndex(); }
+};
+
+struct ORBSLAM3Sim3OptAccess {
+    using KeyFrame = ORB_SLAM3::KeyFrame;
+    using MapPoint = ORB_SLAM3::MapPoint;
+    using Sim3 = g2o::Sim3;
+    using Matrix7d = Eigen::Matrix<double, 7, 7>;
+    static std::vector<MapPoint*> MapPointMatches(KeyFrame* k) { return k->GetMapPointMatches(); }
+    static bool IsBad(MapPoint* p) { return p->isBad(); }
+    static int IndexInKeyFrame(MapPoint* p, KeyFrame* k) { return std::get<0>(p->GetIndexInKeyFrame(k)); }
+    static void Pose(KeyFrame* k, float R[9], float t[3]) {
+        const Eigen::Matrix3f Rcw = k->GetRotation();
+        const Eigen::Vector3f tcw = k->GetTranslation();
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) R[3 * r + c] = Rcw(r, c);
+            t[r] = tcw(r);
+        }
+    }
+    static void WorldPos(MapPoint* p, float X[3]) {
+        const Eigen::Vector3f x = p->GetWorldPos();
+        X[0] = x(0); X[1] = x(1); X[2] = x(2);
+    }
+    static void KeyUn(KeyFrame* k, int i, float* x, float* y, int* octave) {
+        const cv::KeyPoint& kp = k->mvKeysUn[i];
+        *x = kp.pt.x; *y = kp.pt.y; *octave = kp.octave;
+    }
+    static float InvLevelSigma2(KeyFrame* k, int octave) { return k->mvInvLevelSigma2[octave]; }
+    static void Pinhole(KeyFrame* k, float K[4]) {
+        for (int i = 0; i < 4; ++i) K[i] = k->mpCamera->getParameter(i);
+    }
+    static void GetSim3(const Sim3& s, double v[8]) {
+        for (int i = 0; i < 8; ++i) v[i] = s[i];
+    }
+    static void SetSim3(Sim3& s, const double v[8]) {
+        for (int i = 0; i < 8; ++i) s[i] = v[i];
+    }
+    static void SetZero(Matrix7d& m) { m = Eigen::MatrixXd::Zero(7, 7); }
 };
 
 }  // namespace orbgpu

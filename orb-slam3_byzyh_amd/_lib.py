@@ -70,6 +70,18 @@ class Sim3Out(ctypes.Structure):  # orb_sim3_out_t
                 ("hyp_mask", ctypes.c_void_p)]
 
 
+class OptSim3Problem(ctypes.Structure):  # orb_optsim3_problem_t
+    _fields_ = [("n", ctypes.c_int32), ("p1c", ctypes.c_void_p), ("p2c", ctypes.c_void_p), ("obs1", ctypes.c_void_p),
+                ("obs2", ctypes.c_void_p), ("inv_sigma2_1", ctypes.c_void_p), ("inv_sigma2_2", ctypes.c_void_p),
+                ("cam1", ctypes.c_float * 4), ("cam2", ctypes.c_float * 4), ("s12", ctypes.c_double * 8),
+                ("th2", ctypes.c_float), ("fix_scale", ctypes.c_int32)]
+
+
+class OptSim3Out(ctypes.Structure):  # orb_optsim3_out_t
+    _fields_ = [("s12_out", ctypes.c_void_p), ("n_in", ctypes.c_void_p), ("n_bad", ctypes.c_void_p),
+                ("inlier", ctypes.c_void_p), ("chi2_12", ctypes.c_void_p), ("chi2_21", ctypes.c_void_p)]
+
+
 class OrbGpuError(RuntimeError):
     def __init__(self, code: int, where: str, msg: str = ""):
         super().__init__(f"{where} failed with status {code}: {msg}")
@@ -151,6 +163,8 @@ PROTOTYPES = {
     "orb_track_reference_kf_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "orb_sim3_ransac": (_i, [_vp, _i, _vp]),
     "orb_sim3_ransac_device": (_i, [_vp, _i, _vp, _vp]),
+    "orb_optimize_sim3": (_i, [_vp, _i, _vp]),
+    "orb_optimize_sim3_device": (_i, [_vp, _i, _vp, _vp]),
     "orb_ba_create": (_i, [ctypes.POINTER(_vp)]),
     "orb_ba_destroy": (_i, [_vp]),
     "orb_ba_optimize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),

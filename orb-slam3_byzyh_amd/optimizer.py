@@ -208,3 +208,82 @@ def pose_optimization(frames, edges):
     check(_lib.load().orb_pose_optimization(len(fr), fr.ctypes.data, len(ed), ed.ctypes.data, poses.ctypes.data,
                                             outl.ctypes.data, inl.ctypes.data), "orb_pose_optimization")
     return poses, outl[:len(ed)].astype(bool), inl[:len(fr)]
+
+
+OPTSIM3_MAX_PAIRS = 1024  # ORB_OPTSIM3_MAX_PAIRS
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.startswith("torch")
+
+
+def optimize_sim3(problems, chi2: bool = False, stream=None):
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:4195-4494) on a batch of gathered loop / merge candidates, on the
+    GPU (orb_optimize_sim3 / orb_optimize_sim3_device).
+
+    problems: a list of dicts with p1c, p2c [n, 3] and obs1, obs2 [n, 2] (float64), inv_sigma2_1, inv_sigma2_2 [n]
+    (float32), cam1, cam2 (fx, fy, cx, cy; pinhole), s12 (8 doubles: qx qy qz qw tx ty tz s), th2, fix_scale.
+    n is at most OPTSIM3_MAX_PAIRS.  The six arrays are numpy (the host form, synchronous) or torch tensors on one
+    GPU (the device form: no host hop, asynchronous on the current stream or `stream`; the results are tensors).
+
+    Returns one dict per problem: s12 [8] (the input when the reference returns 0 through its < 10 exit), n_in
+    (the reference's return value), n_bad (the first cull's), inlier [n] (where vpMatches1 stays set) and, with
+    chi2=True, chi2_12 / chi2_21 [n]."""
+    lib = _lib.load()
+    problems = list(problems)
+    k = len(problems)
+    if k == 0:
+        check(lib.orb_optimize_sim3(None, 0, None), "orb_optimize_sim3")
+        return []
+    keys = ("p1c", "p2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")
+    device = _is_torch(problems[0]["p1c"])
+    if any(_is_torch(p[key]) != device for p in problems for key in keys):
+        raise TypeError("optimize_sim3: numpy arrays or torch tensors, not a mixture")
+    probs, outs = (_lib.OptSim3Problem * k)(), (_lib.OptSim3Out * k)()
+    keep, results = [], []
+    if device:
+        import torch
+    for i, p in enumerate(problems):
+        if device:
+            if any(not p[key].is_cuda for key in keys):
+                raise ValueError("optimize_sim3: torch tensors must live on the GPU")
+            a = [p[key].to(torch.float64 if j < 4 else torch.float32).contiguous() for j, key in enumerate(keys)]
+            dev = a[0].device
+            new = lambda shape, dt: torch.zeros(shape, dtype=getattr(torch, dt), device=dev)  # noqa: E731
+            ptr = lambda t: t.data_ptr()  # noqa: E731
+        else:
+            a = [np.ascontiguousarray(p[key], np.float64 if j < 4 else np.float32) for j, key in enumerate(keys)]
+            new = lambda shape, dt: np.zeros(shape, dt)  # noqa: E731
+            ptr = lambda t: t.ctypes.data  # noqa: E731
+        n = int(a[0].shape[0])
+        shapes = [(n, 3), (n, 3), (n, 2), (n, 2), (n,), (n,)]
+        if any(tuple(t.shape) != s for t, s in zip(a, shapes)):
+            raise ValueError("optimize_sim3: p1c / p2c [n, 3], obs1 / obs2 [n, 2], inv_sigma2 [n]")
+        cam1, cam2 = [float(c) for c in p["cam1"]], [float(c) for c in p["cam2"]]
+        s12 = [float(v) for v in p["s12"]]
+        if len(cam1) != 4 or len(cam2) != 4 or len(s12) != 8:
+            raise ValueError("optimize_sim3: a camera is (fx, fy, cx, cy), s12 is qx qy qz qw tx ty tz s")
+        r = {"s12": new((8,), "float64"), "n_in": new((1,), "int32"), "n_bad": new((1,), "int32"),
+             "inlier": new((max(n, 1),), "uint8")}
+        if chi2:
+            r["chi2_12"], r["chi2_21"] = new((max(n, 1),), "float64"), new((max(n, 1),), "float64")
+        probs[i] = _lib.OptSim3Problem(n, *[ptr(t) for t in a], (ctypes.c_float * 4)(*cam1), (ctypes.c_float * 4)(*cam2),
+                                       (ctypes.c_double * 8)(*s12), float(p["th2"]), int(bool(p["fix_scale"])))
+        outs[i] = _lib.OptSim3Out(ptr(r["s12"]), ptr(r["n_in"]), ptr(r["n_bad"]), ptr(r["inlier"]),
+                                  ptr(r["chi2_12"]) if chi2 else None, ptr(r["chi2_21"]) if chi2 else None)
+        keep.append(a)
+        for key in ("inlier", "chi2_12", "chi2_21"):
+            if key in r:
+                r[key] = r[key][:n]
+        results.append(r)
+    if device:
+        if stream is None:
+            stream = torch.cuda.current_stream(keep[0][0].device).cuda_stream
+        check(lib.orb_optimize_sim3_device(probs, k, outs, ctypes.c_void_p(stream)), "orb_optimize_sim3_device")
+        for r, a in zip(results, keep):
+            r["_inputs"] = a  # the call is asynchronous: the converted inputs live as long as the results
+    else:
+        check(lib.orb_optimize_sim3(probs, k, outs), "orb_optimize_sim3")
+        for r in results:
+            r["n_in"], r["n_bad"], r["inlier"] = int(r["n_in"][0]), int(r["n_bad"][0]), r["inlier"].astype(bool)
+    return results
