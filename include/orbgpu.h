@@ -523,6 +523,78 @@ int orb_fuse_device(orb_matcher_t m, const orb_fuse_kf_device_t* kfs, int n_kfs,
                     const orb_fuse_points_device_t* points, const uint8_t* d_skip, float th, int32_t* d_best_idx,
                     int32_t* d_best_dist, void* stream);
 
+/* ---- Loop closing's Sim3 searches, batched (src/LoopClosing.cc:976, :1005, :1265, :2712, :2765) --------
+ * ORBmatcher::SearchByProjection(KF, Scw, vpPoints, vpMatched, th, ratioHamming) (src/ORBmatcher.cc:496-619),
+ * its overload that also fills vpMatchedKF (:621-733) and the search half of ORBmatcher::Fuse(KF, Scw,
+ * vpPoints, th, vpReplacePoint) (:1547-1651).  A job is one call of one of them: keyframe kfs[kf], the pose
+ * (Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), Ow = Tcw.inverse().translation(), both
+ * computed by the caller), the points pool[first .. first + count), th, ratioHamming and a mode.  Jobs of one
+ * call may share a keyframe (one keyframe against B candidate poses) or a point range (ten keyframes against
+ * one window); the number of kernel launches does not depend on the job count.  Single pinhole camera
+ * (NLeft == -1).  Per point p of job b, in the reference's order: skipped when skip[] is set; Pc = Rcw P +
+ * tcw; Pc.z < 0 rejected; (u, v) by the mode; KeyFrame::IsInImage (half open: u >= min_x && u < max_x, v
+ * likewise); the distance to Ow inside [0.8 mfMinDistance, 1.2 mfMaxDistance]; PO . normal >= 0.5 dist;
+ * MapPoint::PredictScale(dist, pKF); radius = th * mvScaleFactors[level]; KeyFrame::GetFeaturesInArea (cells
+ * ix outer, iy inner, a cell's keypoints in index order, |dx| < r && |dy| < r); per keypoint the octave in
+ * [level - 1, level]; the first minimum of DescriptorDistance.  There is no chi-square gate and no u_R.
+ * Float arithmetic as the reference build contracts it (oracle/orb_projection_oracle.cpp).
+ *   ORB_S3P_CLAIM_PROJECT  (:496)  u = fx * Pc.x / Pc.z + cx (Pinhole::project).  Points are taken in order, a
+ *                          keypoint that an earlier point of the job matched, or that taken0 flags
+ *                          (vpMatched[idx] != NULL before the call), is skipped by every later point (:589);
+ *                          a match needs (float)bestDist <= 50 * ratioHamming.
+ *   ORB_S3P_CLAIM_INVZ     (:621)  the same with invz = 1 / Pc.z, x = Pc.x * invz, u = fx * x + cx (one fma).
+ *   ORB_S3P_FUSE           (:1547) Pinhole::project, no claims, bestDist <= 50; ratio_hamming and taken0 are
+ *                          not read.  The map mutation (:1655-1672) stays with the caller.
+ * Outputs.  The points of job b sit at off(b) + p, off(b) = the sum of the counts of the jobs before b, in
+ * skip, best_idx and best_dist (sum-of-counts entries each); matched and taken0 have `stride` entries per
+ * job, stride >= every keyframe's N (capacity, for the device entry).
+ *   matched[b * stride + j]  the point p of job b that was matched to keypoint j, or -1 (also where taken0 is
+ *                            set, past the keyframe's count, and everywhere for a FUSE job);
+ *   nmatches[b]              the reference's return value (for FUSE: the points with bestDist <= 50, nFused);
+ *   best_idx[off(b) + p]     the keypoint point p was matched to, or -1;
+ *   best_dist[off(b) + p]    claim modes: the distance of that match, 256 without one; FUSE: the minimum
+ *                            found, as orb_fuse reports it (256 when none, skipped or gated).
+ * The result is the sequential loop's for any input: nothing is truncated.
+ * Limits: n_jobs <= 65535, n_kfs <= 1024, N / cap <= 16384, pool <= 2^20 points, at most 2^24 points over all
+ * jobs (ORB_ERR_CAPACITY beyond); nlevels <= 12, th > 0, 0 < 50 * ratioHamming < 256 in the claim modes
+ * (ORB_ERR_ARG).  Every argument is checked before anything is launched or written. */
+enum { ORB_S3P_CLAIM_PROJECT = 0, ORB_S3P_CLAIM_INVZ = 1, ORB_S3P_FUSE = 2 };
+
+typedef struct orb_sim3_projection_kf {
+    orb_frame_view_t frame;         /* N, mvKeysUn, mDescriptors, bounds, grid inverses, camera, levels,
+                                       mvScaleFactors (u_right, bf, b and Tcw are not read) */
+    float log_scale_factor;         /* mfLogScaleFactor */
+} orb_sim3_projection_kf_t;
+
+/* The same around a device-resident keyframe: the count is read on the device; a negative or over-cap
+ * count gives an empty result for every job of that keyframe.  scale_factors is a host array. */
+typedef struct orb_sim3_projection_kf_device {
+    orb_frame_device_t frame;
+    float log_scale_factor;
+} orb_sim3_projection_kf_device_t;
+
+typedef struct orb_sim3_projection_job {
+    int32_t kf;                     /* index into kfs */
+    int32_t first, count;           /* the job's points: pool[first .. first + count) */
+    int32_t mode;                   /* ORB_S3P_* */
+    float th, ratio_hamming;
+    float Tcw[12];                  /* 3x4 row-major [R | t] of the SE3 taken from Scw */
+    float Ow[3];                    /* its camera centre */
+} orb_sim3_projection_job_t;
+
+/* Host memory, synchronous, through the handle's staging buffers and stream.  skip (isBad() ||
+ * spAlreadyFound.count(pMP)), taken0 and best_dist may be NULL.  n_jobs == 0: ORB_OK, nothing written. */
+int orb_sim3_projection(orb_matcher_t m, const orb_sim3_projection_kf_t* kfs, int n_kfs,
+                        const orb_sim3_projection_job_t* jobs, int n_jobs, const orb_fuse_points_t* pool,
+                        const uint8_t* skip, const uint8_t* taken0, int stride, int32_t* matched, int32_t* nmatches,
+                        int32_t* best_idx, int32_t* best_dist);
+/* The same on device arrays (the job records stay on the host), asynchronous on `stream`; scratch is
+ * allocated and freed on `stream`. */
+int orb_sim3_projection_device(orb_matcher_t m, const orb_sim3_projection_kf_device_t* kfs, int n_kfs,
+                               const orb_sim3_projection_job_t* jobs, int n_jobs, const orb_fuse_points_device_t* pool,
+                               const uint8_t* d_skip, const uint8_t* d_taken0, int stride, int32_t* d_matched,
+                               int32_t* d_nmatches, int32_t* d_best_idx, int32_t* d_best_dist, void* stream);
+
 /* ---- LocalMapping::CreateNewMapPoints, the triangulation half (src/LocalMapping.cc:626-910) ----------
  * For every match (idx1, idx2 = matches12[p][idx1] >= 0) of keyframe 1 against neighbour p, in one call:
  * the parallax test (:720-783), GeometricTools::Triangulate (src/GeometricTools.cc:63-90) or

@@ -10,6 +10,9 @@
  *   int SearchByProjection(Frame& F, const vector<MapPoint*>&, th, bFarPoints, thFarPoints) (:46-240)
  *   int SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)   (:260-494)
  *   int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th = 3.0)          (:1326-1534, bRight = false)
+ *   int SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming)            (:496-619)
+ *   int SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)  (:621-733)
+ *   int Fuse(KeyFrame*, Sim3f& Scw, vpPoints, th, vpReplacePoint)  (:1547-1676), and batched forms of the three
  *   void Fuse(const vector<KeyFrame*>&, const vector<MapPoint*>&, th, vector<int>& vnFused)   (the forward loop
  *                                                             of SearchInNeighbors, src/LocalMapping.cc:991-1001)
  *
@@ -67,12 +70,14 @@
 #ifndef ORBGPU_MATCHER_HPP
 #define ORBGPU_MATCHER_HPP
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <tuple>
 #include <utility>
@@ -509,6 +514,86 @@ public:
         }
     }
 
+    // ---- Loop closing's Sim3 searches (src/ORBmatcher.cc:496-619, :621-733, :1547-1676; called from
+    // src/LoopClosing.cc:976, :1005, :1265, :2712, :2765), through orb_sim3_projection.  S is the Sim3 type
+    // (Sophus::Sim3f); accessor members used besides those of Fuse:
+    //   static void Sim3Pose(const S& Scw, float Tcw[12], float Ow[3]);   // the reference's two Sophus lines,
+    //       verbatim: Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) as 3x4 row-major
+    //       [R | t], Ow = Tcw.inverse().translation() -- so that Sophus's arithmetic stays the reference's
+    //   static std::set<MapPoint*> MapPointSet(KeyFrame*);                // GetMapPoints() (Fuse's spAlreadyFound)
+    // The shim builds skip = isBad() || spAlreadyFound.count(pMP) and taken0 = vpMatched[idx] != NULL, writes
+    // vpMatched / vpMatchedKF from matched[] and returns nmatches.  On a failure: 0, nothing written.
+    template <class S>
+    int SearchByProjection(KeyFrame* pKF, S& Scw, const std::vector<MapPoint*>& vpPoints, std::vector<MapPoint*>& vpMatched,
+                           int th, float ratioHamming = 1.0f) {
+        std::vector<Sim3Call> calls{MakeCall(pKF, Scw, &vpPoints, &vpMatched, ORB_S3P_CLAIM_PROJECT, (float)th, ratioHamming)};
+        Sim3Result r;
+        if (!RunSim3(calls, r)) return 0;
+        for (size_t j = 0; j < vpMatched.size(); ++j)
+            if (r.Matched(0, j) >= 0) vpMatched[j] = vpPoints[r.Matched(0, j)];
+        return r.nmatches[0];
+    }
+    template <class S>
+    int SearchByProjection(KeyFrame* pKF, S& Scw, const std::vector<MapPoint*>& vpPoints,
+                           const std::vector<KeyFrame*>& vpPointsKFs, std::vector<MapPoint*>& vpMatched,
+                           std::vector<KeyFrame*>& vpMatchedKF, int th, float ratioHamming = 1.0f) {
+        if (vpPointsKFs.size() != vpPoints.size() || vpMatchedKF.size() != vpMatched.size())
+            return ShimArgError("SearchByProjection: vpPointsKFs / vpMatchedKF sizes differ from vpPoints / vpMatched");
+        std::vector<Sim3Call> calls{MakeCall(pKF, Scw, &vpPoints, &vpMatched, ORB_S3P_CLAIM_INVZ, (float)th, ratioHamming)};
+        Sim3Result r;
+        if (!RunSim3(calls, r)) return 0;
+        for (size_t j = 0; j < vpMatched.size(); ++j)
+            if (r.Matched(0, j) >= 0) {
+                vpMatched[j] = vpPoints[r.Matched(0, j)];
+                vpMatchedKF[j] = vpPointsKFs[r.Matched(0, j)];
+            }
+        return r.nmatches[0];
+    }
+    // B calls of the first form in one launch (the candidate loop of DetectCommonRegionsFromBoW, the covisible
+    // keyframes of FindMatchesByProjection's verification): job b is SearchByProjection(vJobs[b].first,
+    // vJobs[b].second, vvpPoints[b], vvpMatched[b], th, ratioHamming).  The calls read no state another call
+    // writes (each has its own vpMatched), so the batch equals the sequence.  vnMatches[b] = its return value.
+    template <class S>
+    void SearchByProjection(const std::vector<std::pair<KeyFrame*, S>>& vJobs, const std::vector<std::vector<MapPoint*>>& vvpPoints,
+                            std::vector<std::vector<MapPoint*>>& vvpMatched, int th, float ratioHamming,
+                            std::vector<int>& vnMatches) {
+        SearchByProjectionBatch<S>(vJobs, vvpPoints, nullptr, vvpMatched, nullptr, th, ratioHamming, vnMatches);
+    }
+    // The same for the second form (vvpPointsKFs[b], vvpMatchedKF[b]).
+    template <class S>
+    void SearchByProjection(const std::vector<std::pair<KeyFrame*, S>>& vJobs, const std::vector<std::vector<MapPoint*>>& vvpPoints,
+                            const std::vector<std::vector<KeyFrame*>>& vvpPointsKFs, std::vector<std::vector<MapPoint*>>& vvpMatched,
+                            std::vector<std::vector<KeyFrame*>>& vvpMatchedKF, int th, float ratioHamming,
+                            std::vector<int>& vnMatches) {
+        SearchByProjectionBatch<S>(vJobs, vvpPoints, &vvpPointsKFs, vvpMatched, &vvpMatchedKF, th, ratioHamming, vnMatches);
+    }
+
+    // Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1547-1676): the search on the device, then step 7
+    // (:1655-1672) here in point order with GetMapPoint(bestIdx) as it stands at that moment -- a keypoint an
+    // earlier point's AddMapPoint filled makes a later point a replacement, as upstream.
+    template <class S>
+    int Fuse(KeyFrame* pKF, S& Scw, const std::vector<MapPoint*>& vpPoints, float th, std::vector<MapPoint*>& vpReplacePoint) {
+        std::vector<std::vector<MapPoint*>*> rep{&vpReplacePoint};
+        std::vector<int> n;
+        FuseBatch<S>({{pKF, Scw}}, vpPoints, th, rep, n);
+        return n[0];
+    }
+    // SearchAndFuse's loop over the corrected keyframes (src/LoopClosing.cc:2697-2740) in one launch: job b is
+    // Fuse(vJobs[b].first, vJobs[b].second, vpPoints, th, vvpReplacePoint[b]).  The keyframes must be distinct:
+    // a call's search reads, of the state a Fuse call writes, only its own keyframe's map points.
+    template <class S>
+    void Fuse(const std::vector<std::pair<KeyFrame*, S>>& vJobs, const std::vector<MapPoint*>& vpPoints, float th,
+              std::vector<std::vector<MapPoint*>>& vvpReplacePoint, std::vector<int>& vnFused) {
+        std::vector<std::vector<MapPoint*>*> rep;
+        if (vvpReplacePoint.size() != vJobs.size()) {
+            vnFused.assign(vJobs.size(), 0);
+            ShimArgError("Fuse: one vpReplacePoint per job");
+            return;
+        }
+        for (auto& v : vvpReplacePoint) rep.push_back(&v);
+        FuseBatch<S>(vJobs, vpPoints, th, rep, vnFused);
+    }
+
     // The neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:603-910) for the neighbours
     // that passed the caller's baseline / median-depth pre-tests (:575-601): the batched
     // orb_search_for_triangulation, then orb_create_new_map_points on its matches, then step 6 (:888-909)
@@ -610,6 +695,170 @@ public:
 private:
     orb_matcher_t Handle() const { return detail::ThreadHandle(mfNNratio, mbCheckOrientation); }
     static bool Failed(int rc, const char* what) { return detail::Failed(rc, what); }
+
+    // one call of a reference Sim3 search, as orb_sim3_projection takes it
+    struct Sim3Call {
+        KeyFrame* kf;
+        const std::vector<MapPoint*>* points;
+        const std::vector<MapPoint*>* matched;  // vpMatched (claim forms), NULL for Fuse
+        orb_sim3_projection_job_t job;
+    };
+    struct Sim3Result {
+        int stride = 1;
+        std::vector<int32_t> matched, nmatches, best_idx, offsets;
+        int32_t Matched(size_t b, size_t j) const { return j < (size_t)stride ? matched[b * stride + j] : -1; }
+    };
+    static int ShimArgError(const char* what) {
+        detail::Failed(ORB_ERR_ARG, what);
+        return 0;
+    }
+    template <class S>
+    static Sim3Call MakeCall(KeyFrame* pKF, const S& Scw, const std::vector<MapPoint*>* points,
+                             const std::vector<MapPoint*>* matched, int mode, float th, float ratio) {
+        Sim3Call c{pKF, points, matched, {}};
+        c.job.mode = mode;
+        c.job.th = th;
+        c.job.ratio_hamming = ratio;
+        A::Sim3Pose(Scw, c.job.Tcw, c.job.Ow);
+        return c;
+    }
+    // Distinct keyframes and point vectors are sent once; skip and taken0 as the reference's loops read them.
+    bool RunSim3(std::vector<Sim3Call>& calls, Sim3Result& r) {
+        const size_t B = calls.size();
+        r.nmatches.assign(B, 0);
+        r.offsets.assign(B + 1, 0);
+        if (B == 0) return true;
+        std::vector<KeyFrame*> kf_list;
+        std::map<KeyFrame*, int> kf_index;
+        std::vector<const std::vector<MapPoint*>*> pt_list;
+        std::map<const std::vector<MapPoint*>*, int> pt_first;
+        std::vector<MapPoint*> pool;
+        for (Sim3Call& c : calls) {
+            if (!c.kf || !A::SingleCamera(c.kf)) {
+                ShimArgError("Sim3 search: null or two-camera keyframe");
+                return false;
+            }
+            if (c.matched && (int)c.matched->size() != A::N(c.kf)) {
+                ShimArgError("Sim3 search: vpMatched.size() != N");
+                return false;
+            }
+            if (!kf_index.count(c.kf)) {
+                kf_index[c.kf] = (int)kf_list.size();
+                kf_list.push_back(c.kf);
+            }
+            if (!pt_first.count(c.points)) {
+                pt_first[c.points] = (int)pool.size();
+                pool.insert(pool.end(), c.points->begin(), c.points->end());
+            }
+            c.job.kf = kf_index[c.kf];
+            c.job.first = pt_first[c.points];
+            c.job.count = (int32_t)c.points->size();
+            r.stride = std::max(r.stride, A::N(c.kf));
+        }
+        std::vector<orb_sim3_projection_kf_t> views(kf_list.size());
+        for (size_t k = 0; k < kf_list.size(); ++k) {
+            const detail::FuseKfStore<A> st(kf_list[k]);
+            views[k].frame = st.view.frame;
+            views[k].log_scale_factor = st.view.log_scale_factor;
+        }
+        const detail::FusePointStore<A> sent(pool);
+        for (size_t b = 0; b < B; ++b) r.offsets[b + 1] = r.offsets[b] + calls[b].job.count;
+        const size_t T = (size_t)r.offsets[B];
+        std::vector<uint8_t> skip(std::max<size_t>(T, 1), 0), taken0(B * r.stride, 0);
+        std::vector<orb_sim3_projection_job_t> jobs(B);
+        for (size_t b = 0; b < B; ++b) {
+            const Sim3Call& c = calls[b];
+            jobs[b] = c.job;
+            std::set<MapPoint*> found;                       // spAlreadyFound (:513-514 / :1562)
+            if (c.matched) {
+                found.insert(c.matched->begin(), c.matched->end());
+                found.erase(static_cast<MapPoint*>(nullptr));
+                for (size_t j = 0; j < c.matched->size(); ++j) taken0[b * r.stride + j] = (*c.matched)[j] ? 1 : 0;
+            } else {
+                found = A::MapPointSet(c.kf);
+            }
+            for (size_t i = 0; i < c.points->size(); ++i)    // :526 / :1576 (a NULL point is skipped, not dereferenced)
+                skip[r.offsets[b] + i] = sent.dead[c.job.first + i] || found.count((*c.points)[i]) ? 1 : 0;
+        }
+        r.matched.assign(B * r.stride, -1);
+        r.best_idx.assign(std::max<size_t>(T, 1), -1);
+        return !Failed(orb_sim3_projection(Handle(), views.data(), (int)views.size(), jobs.data(), (int)B, &sent.view,
+                                           skip.data(), taken0.data(), r.stride, r.matched.data(), r.nmatches.data(),
+                                           r.best_idx.data(), nullptr),
+                       "orb_sim3_projection");
+    }
+    template <class S>
+    void SearchByProjectionBatch(const std::vector<std::pair<KeyFrame*, S>>& vJobs,
+                                 const std::vector<std::vector<MapPoint*>>& vvpPoints,
+                                 const std::vector<std::vector<KeyFrame*>>* vvpPointsKFs,
+                                 std::vector<std::vector<MapPoint*>>& vvpMatched, std::vector<std::vector<KeyFrame*>>* vvpMatchedKF,
+                                 int th, float ratioHamming, std::vector<int>& vnMatches) {
+        const size_t B = vJobs.size();
+        vnMatches.assign(B, 0);
+        bool ok = vvpPoints.size() == B && vvpMatched.size() == B &&
+                  (!vvpPointsKFs || (vvpPointsKFs->size() == B && vvpMatchedKF && vvpMatchedKF->size() == B));
+        for (size_t b = 0; ok && vvpPointsKFs && b < B; ++b)
+            ok = (*vvpPointsKFs)[b].size() == vvpPoints[b].size() && (*vvpMatchedKF)[b].size() == vvpMatched[b].size();
+        if (!ok) {
+            ShimArgError("SearchByProjection: one point / match vector per job, of matching sizes");
+            return;
+        }
+        std::vector<Sim3Call> calls;
+        for (size_t b = 0; b < B; ++b)
+            calls.push_back(MakeCall(vJobs[b].first, vJobs[b].second, &vvpPoints[b], &vvpMatched[b],
+                                     vvpPointsKFs ? ORB_S3P_CLAIM_INVZ : ORB_S3P_CLAIM_PROJECT, (float)th, ratioHamming));
+        Sim3Result r;
+        if (!RunSim3(calls, r)) return;
+        for (size_t b = 0; b < B; ++b) {
+            for (size_t j = 0; j < vvpMatched[b].size(); ++j) {
+                const int32_t i = r.Matched(b, j);
+                if (i < 0) continue;
+                vvpMatched[b][j] = vvpPoints[b][i];
+                if (vvpPointsKFs) (*vvpMatchedKF)[b][j] = (*vvpPointsKFs)[b][i];
+            }
+            vnMatches[b] = r.nmatches[b];
+        }
+    }
+    template <class S>
+    void FuseBatch(const std::vector<std::pair<KeyFrame*, S>>& vJobs, const std::vector<MapPoint*>& vpPoints, float th,
+                   const std::vector<std::vector<MapPoint*>*>& rep, std::vector<int>& vnFused) {
+        const size_t B = vJobs.size(), n = vpPoints.size();
+        vnFused.assign(B, 0);
+        std::set<KeyFrame*> distinct;
+        for (size_t b = 0; b < B; ++b) {
+            distinct.insert(vJobs[b].first);
+            if (rep[b]->size() != n) {
+                ShimArgError("Fuse: vpReplacePoint.size() != vpPoints.size()");
+                return;
+            }
+        }
+        if (distinct.size() != B) {
+            ShimArgError("Fuse: the keyframes of a batch must be distinct");
+            return;
+        }
+        std::vector<Sim3Call> calls;
+        for (size_t b = 0; b < B; ++b) calls.push_back(MakeCall(vJobs[b].first, vJobs[b].second, &vpPoints, nullptr, ORB_S3P_FUSE, th, 1.0f));
+        Sim3Result r;
+        if (!RunSim3(calls, r)) return;
+        for (size_t b = 0; b < B; ++b) {
+            KeyFrame* pKF = vJobs[b].first;
+            int nFused = 0;
+            for (size_t iMP = 0; iMP < n; ++iMP) {  // step 7 (:1655-1672)
+                const int32_t bestIdx = r.best_idx[r.offsets[b] + iMP];
+                if (bestIdx < 0) continue;
+                MapPoint* pMP = vpPoints[iMP];
+                MapPoint* pMPinKF = A::GetMapPoint(pKF, bestIdx);
+                if (pMPinKF) {
+                    if (!A::IsBad(pMPinKF)) (*rep[b])[iMP] = pMPinKF;
+                } else {
+                    A::AddObservation(pMP, pKF, bestIdx);
+                    A::AddMapPoint(pKF, pMP, bestIdx);
+                }
+                ++nFused;
+            }
+            vnFused[b] = nFused;
+        }
+    }
 };
 
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:438-529) for a batch of map points in one
@@ -771,6 +1020,16 @@ struct ORBSLAM3MatcherAccess {
         std::unique_lock<std::mutex> lock(p->mMutexPos);
         return p->mfMaxDistance;
     }
+    // Loop closing's Sim3 searches: the reference's two lines (src/ORBmatcher.cc:508-509), verbatim
+    static void Sim3Pose(const Sophus::Sim3f& Scw, float Tcw[12], float Ow[3]) {
+        Sophus::SE3f T = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+        Eigen::Vector3f O = T.inverse().translation();
+        const Eigen::Matrix<float, 3, 4> M = T.matrix3x4();
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) Tcw[4 * r + c] = M(r, c);
+        for (int r = 0; r < 3; ++r) Ow[r] = O(r);
+    }
+    static std::set<MapPoint*> MapPointSet(KeyFrame* k) { return k->GetMapPoints(); }
     // CreateNewMapPoints (mfMinDistance / mfMaxDistance through the friend declaration, as above)
     static void NewPointsGeometry(KeyFrame* k, orb_newpoints_kf_extra_t* e) {
         const Eigen::Matrix<float, 3, 4> T = k->GetPose().matrix3x4();

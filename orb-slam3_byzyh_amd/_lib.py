@@ -130,6 +130,8 @@ PROTOTYPES = {
     "orb_search_by_bow_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "orb_fuse": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp]),
     "orb_fuse_device": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),
+    "orb_sim3_projection": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "orb_sim3_projection_device": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "orb_create_new_map_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "orb_create_new_map_points_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "orb_search_by_projection_frame": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp]),

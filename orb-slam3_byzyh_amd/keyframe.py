@@ -271,6 +271,16 @@ class FuseKfView(ctypes.Structure):  # orb_fuse_kf_t
                 ("log_scale_factor", ctypes.c_float)]
 
 
+class Sim3ProjKfView(ctypes.Structure):  # orb_sim3_projection_kf_t
+    _fields_ = [("frame", FrameView), ("log_scale_factor", ctypes.c_float)]
+
+
+class Sim3ProjJob(ctypes.Structure):  # orb_sim3_projection_job_t
+    _fields_ = [("kf", ctypes.c_int32), ("first", ctypes.c_int32), ("count", ctypes.c_int32), ("mode", ctypes.c_int32),
+                ("th", ctypes.c_float), ("ratio_hamming", ctypes.c_float), ("Tcw", ctypes.c_float * 12),
+                ("Ow", ctypes.c_float * 3)]
+
+
 class FusePointsView(ctypes.Structure):  # orb_fuse_points_t / orb_fuse_points_device_t
     _fields_ = [("n", ctypes.c_int32), ("pos", ctypes.c_void_p), ("normal", ctypes.c_void_p),
                 ("min_dist", ctypes.c_void_p), ("max_dist", ctypes.c_void_p), ("desc", ctypes.c_void_p)]

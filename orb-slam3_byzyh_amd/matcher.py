@@ -9,11 +9,23 @@ from . import _lib
 from ._lib import check
 from .keyframe import (NEWPOINT_DTYPE, DeviceKeyFrame, Frame, FuseKfView, FusePoints, FusePointsView, KeyFrame,
                        KfDeviceView, KfView, LocalMapPoints, NewPointsKf, NewPointsKfDevice, NewPointsOut,
-                       NewPointsParams, PairGeom)
+                       NewPointsParams, PairGeom, Sim3ProjJob, Sim3ProjKfView)
 
 TH_HIGH = 100  # src/ORBmatcher.cc:36
 TH_LOW = 50    # src/ORBmatcher.cc:37
 HISTO_LENGTH = 30  # src/ORBmatcher.cc:38
+# the modes of a SearchByProjectionSim3 job (ORB_S3P_* of include/orbgpu.h)
+ORB_S3P_CLAIM_PROJECT, ORB_S3P_CLAIM_INVZ, ORB_S3P_FUSE = 0, 1, 2
+
+
+def sim3_pose(R, t, s):
+    """(Tcw [3, 4], Ow [3]) in float32 of a Sim3 (R, t, s) as loop closing's searches decompose it
+    (src/ORBmatcher.cc:508-509): Tcw = [R | t / s], Ow = -R^T (t / s).  For tests and callers without Sophus; a
+    C++ caller runs the reference's two Sophus lines (GpuORBmatcher's adapter)."""
+    R = np.asarray(R, np.float32).reshape(3, 3)
+    ts = (np.asarray(t, np.float32).reshape(3) / np.float32(s)).astype(np.float32)
+    Ow = -(R.T @ ts).astype(np.float32)
+    return np.concatenate([R, ts[:, None]], axis=1).astype(np.float32), Ow.astype(np.float32)
 
 
 class ORBmatcher:
@@ -228,6 +240,106 @@ class ORBmatcher:
                                           float(th), out[0].data_ptr(), out[1].data_ptr(),
                                           ctypes.c_void_p(st.cuda_stream)), "orb_fuse_device")
         return out[0][:K, :n], out[1][:K, :n]
+
+    @staticmethod
+    def _sim3_jobs(jobs, n_kfs):
+        """The ctypes job records of SearchByProjectionSim3[Device] and the point offsets [B + 1]."""
+        jobs = list(jobs)
+        B = len(jobs)
+        arr = (Sim3ProjJob * max(B, 1))()
+        offs = np.zeros(B + 1, np.int64)
+        for b, j in enumerate(jobs):
+            a = arr[b]
+            a.kf, a.first, a.count, a.mode = int(j["kf"]), int(j["first"]), int(j["count"]), int(j["mode"])
+            a.th, a.ratio_hamming = float(np.float32(j["th"])), float(np.float32(j.get("ratio", 1.0)))
+            a.Tcw[:] = [float(x) for x in np.asarray(j["Tcw"], np.float32).reshape(12)]
+            a.Ow[:] = [float(x) for x in np.asarray(j["Ow"], np.float32).reshape(3)]
+            offs[b + 1] = offs[b] + max(a.count, 0)
+        return arr, offs
+
+    def SearchByProjectionSim3(self, kfs, jobs, points: FusePoints, skip=None, taken0=None, stride=None):
+        """Loop closing's three Sim3 searches (src/ORBmatcher.cc:496-619, :621-733 and the search half of Fuse,
+        :1547-1651), batched (orb_sim3_projection).  kfs: Frame objects (a list).  jobs: dicts, one per call of
+        a reference function: kf (index into kfs), first / count (the job's points in the pool `points`), mode
+        (ORB_S3P_CLAIM_PROJECT, ORB_S3P_CLAIM_INVZ or ORB_S3P_FUSE), th, ratio (ratioHamming, default 1.0), Tcw
+        (3 x 4) and Ow (3) as sim3_pose gives them.  skip: uint8, one flag per point of every job in job order
+        (isBad() || spAlreadyFound.count(pMP)), or None; taken0: uint8 [B, stride], vpMatched[idx] != NULL before
+        the call, or None; stride (default: the largest N) is the row length of `matched`.  Returns a dict:
+        matched [B, stride] (the point of the job matched to each keypoint, -1 none), nmatches [B], best_idx and
+        best_dist (one entry per point of every job, in job order) and offsets [B + 1] (job b's points are
+        offsets[b] : offsets[b + 1]).  All int32 but offsets."""
+        kfs = [kfs] if isinstance(kfs, Frame) else list(kfs)
+        K = len(kfs)
+        arr, offs = self._sim3_jobs(jobs, K)
+        B, T = len(offs) - 1, int(offs[-1])
+        if stride is None:
+            stride = max([k.N for k in kfs] + [1])
+        out = dict(matched=np.full((max(B, 1), stride), -1, np.int32), nmatches=np.zeros(max(B, 1), np.int32),
+                   best_idx=np.full(max(T, 1), -1, np.int32), best_dist=np.full(max(T, 1), 256, np.int32))
+        sk = tk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+            if sk.size != T:
+                raise ValueError("skip: one flag per point of every job")
+        if taken0 is not None:
+            tk = np.ascontiguousarray(taken0, dtype=np.uint8)
+            if tk.shape != (B, stride):
+                raise ValueError("taken0: [jobs, stride] flags")
+        views = (Sim3ProjKfView * max(K, 1))()
+        for k, kf in enumerate(kfs):
+            kf.fuse_view()  # (fills mfLogScaleFactor's default)
+            views[k] = Sim3ProjKfView(kf.view(), kf.mfLogScaleFactor)
+        check(_lib.load().orb_sim3_projection(self._handle(), views, K, arr, B, ctypes.byref(points.view()),
+                                              None if sk is None else sk.ctypes.data,
+                                              None if tk is None else tk.ctypes.data, int(stride),
+                                              out["matched"].ctypes.data, out["nmatches"].ctypes.data,
+                                              out["best_idx"].ctypes.data, out["best_dist"].ctypes.data),
+              "orb_sim3_projection")
+        return dict(matched=out["matched"][:B], nmatches=out["nmatches"][:B], best_idx=out["best_idx"][:T],
+                    best_dist=out["best_dist"][:T], offsets=offs)
+
+    def SearchByProjectionSim3Device(self, kfs, jobs, points, skip=None, taken0=None, stride=None,
+                                     log_scale_factor=None, stream=None, out=None):
+        """The same on device-resident keyframes and points (orb_sim3_projection_device), asynchronous on
+        `stream`.  kfs: tracking.DeviceFrame objects (counts read on the device; a flagged count gives an empty
+        result for every job of that keyframe); points: CUDA tensors (pos [n, 3], normal [n, 3], min_dist [n],
+        max_dist [n] float32, desc [n, 32] uint8); skip / taken0: uint8 CUDA tensors or None; stride (default:
+        the largest capacity); log_scale_factor: mfLogScaleFactor (None: logf(mvScaleFactors[1])).  Returns the
+        dict of SearchByProjectionSim3 with CUDA tensors (offsets stays a numpy array), which `out` reuses."""
+        import torch
+        from .keyframe import logf
+        from .tracking import FrameDeviceView, Sim3ProjKfDeviceView  # (tracking imports this module)
+
+        kfs = list(kfs)
+        K = len(kfs)
+        pos, normal, min_dist, max_dist, desc = (t.contiguous() for t in points)
+        n, dev = int(pos.shape[0]), pos.device
+        arr, offs = self._sim3_jobs(jobs, K)
+        B, T = len(offs) - 1, int(offs[-1])
+        if stride is None:
+            stride = max([k.cap for k in kfs] + [1])
+        if out is None:
+            out = dict(matched=torch.empty((max(B, 1), stride), dtype=torch.int32, device=dev),
+                       nmatches=torch.empty(max(B, 1), dtype=torch.int32, device=dev),
+                       best_idx=torch.empty(max(T, 1), dtype=torch.int32, device=dev),
+                       best_dist=torch.empty(max(T, 1), dtype=torch.int32, device=dev))
+        views = (Sim3ProjKfDeviceView * max(K, 1))()
+        for k, kf in enumerate(kfs):
+            lsf = logf(kf.mvScaleFactors[1]) if log_scale_factor is None else log_scale_factor
+            ctypes.memmove(ctypes.byref(views[k].frame), ctypes.byref(kf.view()), ctypes.sizeof(FrameDeviceView))
+            views[k].log_scale_factor = float(np.float32(lsf))
+        pv = FusePointsView(n, pos.data_ptr(), normal.data_ptr(), min_dist.data_ptr(), max_dist.data_ptr(), desc.data_ptr())
+        sk = None if skip is None else skip.contiguous()
+        tk = None if taken0 is None else taken0.contiguous()
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        check(_lib.load().orb_sim3_projection_device(self._handle(), views, K, arr, B, ctypes.byref(pv),
+                                                     None if sk is None else sk.data_ptr(),
+                                                     None if tk is None else tk.data_ptr(), int(stride),
+                                                     out["matched"].data_ptr(), out["nmatches"].data_ptr(),
+                                                     out["best_idx"].data_ptr(), out["best_dist"].data_ptr(),
+                                                     ctypes.c_void_p(st.cuda_stream)), "orb_sim3_projection_device")
+        return dict(matched=out["matched"][:B], nmatches=out["nmatches"][:B], best_idx=out["best_idx"][:T],
+                    best_dist=out["best_dist"][:T], offsets=offs)
 
     @staticmethod
     def _newpoints_params(pKF1, inertial, far_points, th_far_points, ratio_factor) -> NewPointsParams:

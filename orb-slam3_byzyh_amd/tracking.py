@@ -67,6 +67,10 @@ class FuseKfDeviceView(ctypes.Structure):  # orb_fuse_kf_device_t (ORBmatcher.Fu
                 ("log_scale_factor", ctypes.c_float)]
 
 
+class Sim3ProjKfDeviceView(ctypes.Structure):  # orb_sim3_projection_kf_device_t (ORBmatcher.SearchByProjectionSim3Device)
+    _fields_ = [("frame", FrameDeviceView), ("log_scale_factor", ctypes.c_float)]
+
+
 class LastPointsDeviceView(ctypes.Structure):  # orb_last_points_device_t
     _fields_ = [("n", ctypes.c_void_p), ("cap", ctypes.c_int32), ("valid", ctypes.c_void_p),
                 ("observed", ctypes.c_void_p), ("xyz", ctypes.c_void_p), ("desc", ctypes.c_void_p),
