@@ -32,7 +32,7 @@ oracle/_build/liborb_oracle.so: $(wildcard oracle/*.cpp) $(wildcard oracle/*.h)
 # (tests/test_shims_gpu.py).  Test programs, built here so that the GPU box runs them without a build.
 SHIM_BINS := build/tests/local_ba_shim_gpu build/tests/matcher_shim_gpu build/tests/cv_shim_gpu \
              build/tests/bow_shim_gpu build/tests/fuse_shim_gpu build/tests/newpoints_shim_gpu build/tests/sim3_shim_gpu \
-             build/tests/optsim3_shim_gpu build/tests/sim3proj_shim_gpu
+             build/tests/optsim3_shim_gpu build/tests/sim3proj_shim_gpu build/tests/bowkf_shim_gpu
 SHIM_FLAGS := -O2 -std=c++17 -ffp-contract=off -pthread -Wall -Werror -Iinclude -Itests/native/mock_cv
 SHIM_LIBS := -L$(LIBDIR) -lorbgpu -Loracle/_build -lorb_oracle \
              -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)' -Wl,-rpath,'$$ORIGIN/../../oracle/_build'
@@ -69,6 +69,11 @@ build/tests/optsim3_shim_gpu: tests/native/optsim3_shim_gpu.cpp $(wildcard inclu
 
 # The Sim3 searches' expected matches come from tests/sim3_projection_ref.py (tests/test_sim3proj_shim_gpu.py)
 build/tests/sim3proj_shim_gpu: tests/native/sim3proj_shim_gpu.cpp $(wildcard include/*.h*) $(LIBDIR)/liborbgpu.so
+	@mkdir -p build/tests
+	g++ $(SHIM_FLAGS) $< -o $@ -L$(LIBDIR) -lorbgpu -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
+
+# The loop-closing BoW shims' expected values come from tests/bow_kf_ref.py (tests/test_bowkf_shim_gpu.py)
+build/tests/bowkf_shim_gpu: tests/native/bowkf_shim_gpu.cpp tests/native/bowkf_mock.h $(wildcard include/*.h*) $(LIBDIR)/liborbgpu.so
 	@mkdir -p build/tests
 	g++ $(SHIM_FLAGS) $< -o $@ -L$(LIBDIR) -lorbgpu -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 

@@ -288,6 +288,34 @@ int orb_search_by_bow_device(orb_matcher_t m, const orb_kf_device_t* kfs, const 
                              const orb_kf_device_t* frames, int n_frames, const int32_t* pair_frame,
                              int32_t* d_matches, int32_t* d_n_matches, void* stream);
 
+/* ---- ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&) (src/ORBmatcher.cc:893-1044) ----
+ * Loop closing's matcher of the current keyframe against each keyframe of a candidate's window
+ * (src/LoopClosing.cc:840-851), single camera (NLeft == -1).  The node walk of the overload above with both
+ * sides masked (ok[i] = 1: the feature's map point is non-NULL and not isBad()), the claim mark on the second
+ * side (vbMatched2, set at acceptance and not released when the rotation check later removes the match), the
+ * result indexed by the first side's features, and the acceptance bestDist1 < TH_LOW, strict, and
+ * (float)bestDist1 < mfNNratio * (float)bestDist2.  The rotation histogram is over idx1 with
+ * kps1[idx1].angle - kps2[bestIdx2].angle and factor 1 / HISTO_LENGTH.
+ *
+ * kf1 against n_pairs second keyframes in one launch (host memory, synchronous).  ok1: kf1->n flags, ok2s[p]:
+ * kf2s[p].n flags (ok1, ok2s or ok2s[p] NULL: the view's has_mappoint; that NULL too: no usable map point).
+ * Writes matches12[p * kf1->n + idx1] = the matched feature of kf2s[p] (vpMatches12[idx1] is the caller's
+ * mvpMapPoints2[that index]) or -1, and n_matches[p] (the return value).  Views are validated as in
+ * orb_search_by_bow. */
+int orb_search_by_bow_kf(orb_matcher_t m, const orb_kf_view_t* kf1, const uint8_t* ok1, const orb_kf_view_t* kf2s,
+                         const uint8_t* const* ok2s, int n_pairs, int32_t* matches12, int32_t* n_matches);
+
+/* The same on device-resident sides, asynchronous on `stream`: pair p searches kf1s[pair_kf1[p]] (pair_kf1
+ * NULL: kf1s[0]) against kf2s[p].  d_ok1[k]: device flags of kf1s[k] (cap entries), d_ok2[p]: of kf2s[p] (either
+ * array or an entry NULL: the side's has_mappoint).  With C = max over kf1s of cap: d_matches12[p * C + idx1]
+ * (-1 past the count), d_n_matches[p].  Counts are read on the device; a side whose *n is negative or above
+ * cap, or whose *n_nodes is negative, gives d_n_matches[p] = ORB_ERR_CAPACITY and an all -1 row.  Every
+ * argument is checked before anything is launched or written; the number of launches does not depend on
+ * n_pairs. */
+int orb_search_by_bow_kf_device(orb_matcher_t m, const orb_kf_device_t* kf1s, int n_kf1, const uint8_t* const* d_ok1,
+                                const orb_kf_device_t* kf2s, const uint8_t* const* d_ok2, const int32_t* pair_kf1,
+                                int n_pairs, int32_t* d_matches12, int32_t* d_n_matches, void* stream);
+
 /* ---- Frame::UndistortKeyPoints (src/Frame.cc:1003-1051): mvKeysUn from mvKeys by cv::undistortPoints
  * (OpenCV 4.x: five fixed-point iterations of the inverse k1 k2 p1 p2 k3 model in double, P = K, the
  * result rounded to float; parity with a real OpenCV build unpinned), on the extractor's device layout:
@@ -1118,6 +1146,78 @@ int orb_sim3_ransac(const orb_sim3_problem_t* problems, int n_problems, const or
  * hypothesis reports hyp_inliers -1 and a NaN transform, and it is never selected. */
 int orb_sim3_ransac_device(const orb_sim3_problem_t* problems, int n_problems, const orb_sim3_out_t* outs,
                            void* stream);
+
+/* ---- The Sim3 problems of loop closing's BoW candidates (src/LoopClosing.cc:855-881, src/Sim3Solver.cc:71-118)
+ * From the matches12 rows of orb_search_by_bow_kf[_device] (the current keyframe KF1 against every keyframe of
+ * every candidate's window) to the arrays orb_sim3_problem_t takes, for n_cand candidates in one call.
+ * Candidate c owns the pairs [group[c], group[c+1]) in window order j.  Map points are indices into one pool
+ * (xyz, and an optional bad flag per point); a keyframe lists its features' points in mp_id (-1: NULL).
+ *
+ * The merge, exactly as :855-881: (j, k) in lexicographic order, a non-bad point not seen yet for the candidate
+ * is inserted: num_bow[c]++ (numBoWMatches), matched_point[c][k] = its id (vpMatchedPoints), matched_pair[c][k]
+ * = j (vpKeyFrameMatchedMP).  A later j that inserts another new point at the same k overwrites the slot and
+ * the count keeps both: num_bow is the number of distinct points, not of filled slots.  pair_ok[p] = 0 (the
+ * window keyframe is NULL or bad, :842) leaves pair p out.
+ *
+ * The gather, as the Sim3Solver constructor (:71-118) for every candidate whatever num_bow is (the gate of
+ * LoopClosing.cc:889 is the caller's): in increasing k the slots with matched_point >= 0, ok1[k] set and the
+ * matched point not bad.  indexKF1 = k and indexKF2 = the matched feature of pair matched_pair[c][k]: this
+ * rests on the map's invariant that a keyframe lists a point at the index the point lists for the keyframe;
+ * a caller that must honour GetIndexInKeyFrame < 0 passes obs_ok.  Entry i < n[c], in that order (the
+ * caller's random triples index it): idx1 (mvnIndices1), x3dc1 = Rcw1 X1w + tcw1, x3dc2 = Rcw2[c] X2w + tcw2[c]
+ * (the candidate's pose for every window keyframe's point, as the reference has it), max_err1 / 2 =
+ * (float)(9.210 * sigma2) of the keypoint's octave in KF1 / in the matched window keyframe (a slot whose keypoint's
+ * octave lies outside 0 .. nlevels-1 on either side, where the reference would read past mvLevelSigma2, is dropped
+ * like one with obs_ok unset).  float32, each
+ * component fma(r2, z, fma(r0, x, r1 * y)) + t, the order of the Sim3 searches.  Entries past n[c] hold idx1 -1
+ * and zeros.  Row c of every per-slot output starts at c * stride (x3dc: 3 * c * stride): the pointers
+ * x3dc1 + 3 c stride, ... go into orb_sim3_problem_t unchanged, with n = n[c]. */
+typedef struct orb_loop_bow_kf {
+    int32_t n;                  /* features (device form: the capacity): the bound of every index into the arrays */
+    const int32_t* mp_id;       /* n: the feature's map point in the pool, -1 = NULL */
+    const orb_keypoint_t* kps;  /* n: mvKeysUn (the octave is read) */
+    const uint8_t* obs_ok;      /* n flags, NULL = all set: the point's GetIndexInKeyFrame(this keyframe) >= 0 */
+    int32_t nlevels;            /* 1 .. 12 */
+    float level_sigma2[12];     /* mvLevelSigma2 */
+} orb_loop_bow_kf_t;
+
+typedef struct orb_loop_bow_in {
+    orb_loop_bow_kf_t kf1;          /* the current keyframe; kf1.n <= stride */
+    const uint8_t* ok1;             /* kf1.n flags: map point non-NULL and not isBad(); NULL: from mp_id and bad */
+    float Tcw1[12];                 /* 3x4 row-major [Rcw1 | tcw1] */
+    int32_t n_pairs, n_cand;        /* <= 65535 each */
+    const orb_loop_bow_kf_t* kf2s;  /* host array, n_pairs: the window keyframes, candidate after candidate */
+    const uint8_t* pair_ok;         /* host array, n_pairs, or NULL (all set) */
+    const int32_t* group;           /* host array, n_cand + 1: group[0] = 0 <= ... <= group[n_cand] = n_pairs */
+    const float* Tcw2;              /* host array, n_cand x 12: the candidates' poses (pMostBoWMatchesKF = pKFi) */
+    int32_t n_points;               /* the pool */
+    const float* xyz;               /* n_points x 3: GetWorldPos() */
+    const uint8_t* bad;             /* n_points flags (isBad()), NULL = none */
+    const int32_t* matches12;       /* n_pairs x stride: row p = SearchByBoW(KF1, window keyframe p) */
+    int32_t stride;                 /* C: the row length of matches12 and of every per-slot output, < 2^20 */
+} orb_loop_bow_in_t;
+
+typedef struct orb_loop_bow_out {
+    int32_t* matched_point;  /* n_cand x stride */
+    int32_t* matched_pair;   /* n_cand x stride: j, or -1 */
+    int32_t* num_bow;        /* n_cand */
+    int32_t* n;              /* n_cand: the problem's correspondences */
+    int32_t* idx1;           /* n_cand x stride */
+    float* x3dc1;            /* n_cand x stride x 3 */
+    float* x3dc2;            /* n_cand x stride x 3 */
+    float* max_err1;         /* n_cand x stride */
+    float* max_err2;         /* n_cand x stride */
+} orb_loop_bow_out_t;
+
+/* Host form: mp_id, kps, obs_ok, ok1, xyz, bad, matches12 and the outputs are host arrays; synchronous, through
+ * the handle's staging buffers.  Device form: those are device arrays (matches12 straight from
+ * orb_search_by_bow_kf_device; the five tables marked `host array` stay on the host), asynchronous on `stream`,
+ * no host hop: the caller reads n back, draws its triples and calls orb_sim3_ransac_device.  Every argument is
+ * checked before anything is launched or written (ORB_ERR_ARG); the number of launches does not depend on
+ * n_pairs or n_cand, and nothing the size of the pool is cleared. */
+int orb_loop_bow_problems(orb_matcher_t m, const orb_loop_bow_in_t* in, const orb_loop_bow_out_t* out);
+int orb_loop_bow_problems_device(orb_matcher_t m, const orb_loop_bow_in_t* in, const orb_loop_bow_out_t* out,
+                                 void* stream);
 
 /* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:4195-4494; called per loop / merge candidate at
  * src/LoopClosing.cc:689 and :991) ------------------------------------------------------------------------

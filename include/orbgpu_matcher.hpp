@@ -9,6 +9,8 @@
  *   int SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono)   (:1951-2185)
  *   int SearchByProjection(Frame& F, const vector<MapPoint*>&, th, bFarPoints, thFarPoints) (:46-240)
  *   int SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPointMatches)   (:260-494)
+ *   int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)  (:893-1044), and its batched
+ *       form over vpCovKFi (src/LoopClosing.cc:840-851; needs A::IsBad(KeyFrame*))
  *   int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, th = 3.0)          (:1326-1534, bRight = false)
  *   int SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming)            (:496-619)
  *   int SearchByProjection(KeyFrame*, Sim3f& Scw, vpPoints, vpPointsKFs, vpMatched, vpMatchedKF, th, ratioHamming)  (:621-733)
@@ -435,6 +437,82 @@ public:
         return n;
     }
 
+    // src/ORBmatcher.cc:893-1044 (LoopClosing::DetectCommonRegionsFromBoW, src/LoopClosing.cc:845).  vpMatches12 is
+    // set to pKF1's map-point count of NULL entries first (:907); entry idx1 then receives pKF2's map point of the
+    // feature matched to pKF1's feature idx1.  A library failure: 0, every entry NULL.
+    int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12) {
+        std::vector<std::vector<MapPoint*>> vv;
+        std::vector<int> n;
+        SearchByBoWPairs(pKF1, std::vector<KeyFrame*>(1, pKF2), vv, n);
+        vpMatches12.swap(vv[0]);
+        return n[0];
+    }
+
+    // The window loop of src/LoopClosing.cc:840-851 in one library call: vvpMatches12[j] and vnMatches[j] are
+    // what SearchByBoW(pKF1, vpKF2s[j], vvpMatches12[j]) gives; a keyframe that is NULL or isBad() is skipped as at
+    // :842 (its vector stays empty, its count 0).  Returns false when the library failed (every count 0).
+    bool SearchByBoW(KeyFrame* pKF1, const std::vector<KeyFrame*>& vpKF2s,
+                     std::vector<std::vector<MapPoint*>>& vvpMatches12, std::vector<int>& vnMatches) {
+        std::vector<KeyFrame*> live;
+        std::vector<size_t> at;
+        for (size_t j = 0; j < vpKF2s.size(); ++j)
+            if (vpKF2s[j] && !A::IsBad(vpKF2s[j])) {
+                live.push_back(vpKF2s[j]);
+                at.push_back(j);
+            }
+        std::vector<std::vector<MapPoint*>> vv;
+        std::vector<int> n;
+        const bool ok = SearchByBoWPairs(pKF1, live, vv, n);
+        vvpMatches12.assign(vpKF2s.size(), std::vector<MapPoint*>());
+        vnMatches.assign(vpKF2s.size(), 0);
+        for (size_t k = 0; k < live.size(); ++k) {
+            vvpMatches12[at[k]].swap(vv[k]);
+            vnMatches[at[k]] = n[k];
+        }
+        return ok;
+    }
+
+    // The same search as feature indices: rows[p * N1 + idx1] = the matched feature of kfs[p] or -1, N1 = pKF1's
+    // feature count (every keyframe non-NULL).  What orbgpu::LoopBowProblems (orbgpu_sim3.hpp) merges.
+    bool SearchByBoWIndices(KeyFrame* pKF1, const std::vector<KeyFrame*>& kfs, std::vector<int32_t>& rows,
+                            std::vector<int32_t>& counts) {
+        const size_t P = kfs.size();
+        detail::KfViewStore<A> v1(pKF1);
+        const int n1 = v1.view.n > 0 ? v1.view.n : 0;
+        rows.assign(P * (size_t)n1 + 1, -1);
+        counts.assign(P + 1, 0);
+        if (P == 0) return true;
+        // ok = pMP && !pMP->isBad() on either side (:939-943, :960-967)
+        auto usable = [](KeyFrame* k, int n) {
+            const std::vector<MapPoint*> mps = A::MapPointMatches(k);
+            std::vector<uint8_t> ok(n > 0 ? n : 1, 0);
+            for (int i = 0; i < n && i < (int)mps.size(); ++i) ok[i] = (mps[i] && !A::IsBad(mps[i])) ? 1 : 0;
+            return ok;
+        };
+        const std::vector<uint8_t> ok1 = usable(pKF1, n1);
+        std::vector<std::unique_ptr<detail::KfViewStore<A>>> stores;
+        std::vector<orb_kf_view_t> views;
+        std::vector<std::vector<uint8_t>> ok2(P);
+        std::vector<const uint8_t*> ok2p(P);
+        for (size_t p = 0; p < P; ++p) {
+            stores.emplace_back(new detail::KfViewStore<A>(kfs[p]));
+            views.push_back(stores.back()->view);
+            ok2[p] = usable(kfs[p], views[p].n);
+            ok2p[p] = ok2[p].data();
+        }
+        if (Failed(orb_search_by_bow_kf(Handle(), &v1.view, ok1.data(), views.data(), ok2p.data(), (int)P, rows.data(),
+                                        counts.data()),
+                   "orb_search_by_bow_kf")) {
+            rows.assign(P * (size_t)n1 + 1, -1);
+            counts.assign(P + 1, 0);
+            return false;
+        }
+        return true;
+    }
+
+    // (for orbgpu::LoopBowProblems: the merge and the gather run through this matcher's handle)
+    orb_matcher_t LibraryHandle() const { return Handle(); }
+
     // src/ORBmatcher.cc:1326-1534 without bRight (two-camera rigs keep the CPU body: Supports(pKF) is false
     // for NLeft != -1).  One orb_fuse call for the search (steps 1-6), then step 7 (:1506-1527) here, in
     // index order, with the skip tests evaluated again at apply time.
@@ -694,6 +772,26 @@ public:
 
 private:
     orb_matcher_t Handle() const { return detail::ThreadHandle(mfNNratio, mbCheckOrientation); }
+
+    // SearchByBoW(pKF1, kfs[p], vv[p]) for every p (all non-NULL): vpMatches12[idx1] = vpMapPoints2[bestIdx2] (:990)
+    bool SearchByBoWPairs(KeyFrame* pKF1, const std::vector<KeyFrame*>& kfs, std::vector<std::vector<MapPoint*>>& vv,
+                          std::vector<int>& n) {
+        const size_t n_mp1 = A::MapPointMatches(pKF1).size();  // :907
+        vv.assign(kfs.size(), std::vector<MapPoint*>(n_mp1, static_cast<MapPoint*>(nullptr)));
+        n.assign(kfs.size(), 0);
+        std::vector<int32_t> rows, counts;
+        if (!SearchByBoWIndices(pKF1, kfs, rows, counts)) return false;
+        const int n1 = A::N(pKF1);
+        for (size_t p = 0; p < kfs.size(); ++p) {
+            const std::vector<MapPoint*> mps2 = A::MapPointMatches(kfs[p]);
+            for (int i = 0; i < n1 && i < (int)n_mp1; ++i) {
+                const int32_t j = rows[p * (size_t)n1 + i];
+                if (j >= 0 && j < (int)mps2.size()) vv[p][i] = mps2[j];
+            }
+            n[p] = counts[p];
+        }
+        return true;
+    }
     static bool Failed(int rc, const char* what) { return detail::Failed(rc, what); }
 
     // one call of a reference Sim3 search, as orb_sim3_projection takes it

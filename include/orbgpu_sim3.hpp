@@ -12,6 +12,12 @@
  *   GetEstimatedTransformation / Rotation / Translation / Scale                                        (:441-459)
  *   static void Batch(const vector<Sim3Solver*>&)   several constructed solvers in one library call: the
  *                                                   candidate loop of LoopClosing::DetectCommonRegionsFromBoW
+ *   orbgpu::LoopBowProblems<A>(matcherBoW, pCurrentKF, vpCandidates, vvpCovKFi, bFixScale, out)
+ *                                                   src/LoopClosing.cc:840-881 and the constructor's gather for a
+ *                                                   list of candidates on the GPU (orb_search_by_bow_kf +
+ *                                                   orb_loop_bow_problems): per candidate vpMatchedPoints,
+ *                                                   vpKeyFrameMatchedMP, numBoWMatches and a ready Sim3Solver<A>
+ *                                                   (needs A::IsBad(KeyFrame*))
  *
  * The hypotheses of a RANSAC do not depend on each other, so the first iterate() evaluates all mRansacMaxIts of
  * them in one library call; every iterate(n) then replays the reference's control flow over the returned counts:
@@ -33,7 +39,7 @@
  *     static Matrix4f Matrix4(const float m[16]);  static Matrix3f Matrix3(const float m[9]);   // row-major
  *     static Vector3f Vector3(const float v[3]);
  *     static std::vector<MapPoint*> MapPointMatches(KeyFrame*);           // GetMapPointMatches()
- *     static bool IsBad(MapPoint*);
+ *     static bool IsBad(MapPoint*);   static bool IsBad(KeyFrame*);       // (the KeyFrame form: LoopBowProblems only)
  *     static int IndexInKeyFrame(MapPoint*, KeyFrame*);                   // get<0>(GetIndexInKeyFrame(pKF))
  *     static const orb_keypoint_t* KeysUn(KeyFrame*);  static const float* LevelSigma2(KeyFrame*);
  *     static void Pose(KeyFrame*, float Rcw[9], float tcw[3]);            // GetRotation(), GetTranslation()
@@ -56,6 +62,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <map>
+#include <memory>
 #include <vector>
 
 #include "orbgpu.h"
@@ -108,6 +116,21 @@ public:
             A::WorldPos(pMP2, X);
             PushCamera(R2, t2, X, mvX3Dc2);
         }
+        A::Pinhole(pKF1, mCam1);
+        A::Pinhole(pKF2, mCam2);
+        SetRansacParameters();
+    }
+
+    // A solver over correspondences the library gathered (orb_loop_bow_problems; LoopBowProblems below): n1 =
+    // vpMatched12.size(), then the n entries of mvnIndices1, mvX3Dc1 / 2 and mvnMaxError1 / 2 in order.
+    Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, int n1, int n, const int32_t* idx1, const float* x3dc1, const float* x3dc2,
+               const float* max_err1, const float* max_err2, const bool bFixScale)
+        : mbFixScale(bFixScale), mN1(n1) {
+        mvnIndices1.assign(idx1, idx1 + n);
+        mvX3Dc1.assign(x3dc1, x3dc1 + 3 * (size_t)n);
+        mvX3Dc2.assign(x3dc2, x3dc2 + 3 * (size_t)n);
+        mvnMaxError1.assign(max_err1, max_err1 + n);
+        mvnMaxError2.assign(max_err2, max_err2 + n);
         A::Pinhole(pKF1, mCam1);
         A::Pinhole(pKF2, mCam2);
         SetRansacParameters();
@@ -189,6 +212,11 @@ public:
     int Iterations() const { return mnIterations; }
     int MaxIterations() const { return mRansacMaxIts; }
     int Correspondences() const { return N; }
+    const std::vector<int>& Indices1() const { return mvnIndices1; }
+    const std::vector<float>& X3Dc1() const { return mvX3Dc1; }
+    const std::vector<float>& X3Dc2() const { return mvX3Dc2; }
+    const std::vector<float>& MaxError1() const { return mvnMaxError1; }
+    const std::vector<float>& MaxError2() const { return mvnMaxError2; }
     const std::vector<int32_t>& Samples() const { return mSamples; }
     const std::vector<int32_t>& HypothesisInliers() const { return mCounts; }
 
@@ -319,6 +347,177 @@ private:
     int32_t mWinner = -1, mBestOfAll = -1;
 };
 
+// What src/LoopClosing.cc:817-899 builds for one candidate.
+template <class A>
+struct LoopBowCandidate {
+    std::vector<typename A::MapPoint*> vpMatchedPoints;      // :831, by the current keyframe's feature
+    std::vector<typename A::KeyFrame*> vpKeyFrameMatchedMP;  // :833
+    int numBoWMatches = 0;                                   // :822: distinct points, not filled slots
+    std::vector<int> vnMatches;                              // SearchByBoW's return value per window keyframe (:845)
+    std::unique_ptr<Sim3Solver<A>> solver;  // Sim3Solver(mpCurrentKF, pKFi, vpMatchedPoints, bFixScale,
+                                            // vpKeyFrameMatchedMP) (:899), gathered on the GPU; NULL on a failure
+};
+
+// src/LoopClosing.cc:840-881 and the Sim3Solver constructor's gather (src/Sim3Solver.cc:71-118) for every
+// candidate of the current keyframe in two library calls: vvpCovKFi[c] is candidate c's window (entries NULL or
+// isBad() are skipped as at :842), vpCandidates[c] the keyframe whose pose and camera the solver takes
+// (pMostBoWMatchesKF = pKFi, :825).  Every candidate gets a solver, whatever numBoWMatches is: the gate of :889
+// stays with the caller, who then calls SetRansacParameters and iterate (or Sim3Solver::Batch first).  Unlike
+// the constructor above, the matched point's keyframe is the window keyframe it came through (what the reference
+// intends with vpKeyFrameMatchedMP); GetIndexInKeyFrame < 0 on either side drops the slot as at :90.
+// Matcher: orbgpu::ORBmatcher<MA> over the same KeyFrame / MapPoint types (matcherBoW of :795).
+// Never throws; returns false when a library call failed (orbgpu::LastShimError()): every candidate then has
+// numBoWMatches 0, all-NULL vectors and no solver.
+template <class A, class Matcher>
+bool LoopBowProblems(Matcher& matcherBoW, typename A::KeyFrame* pCurrentKF,
+                     const std::vector<typename A::KeyFrame*>& vpCandidates,
+                     const std::vector<std::vector<typename A::KeyFrame*>>& vvpCovKFi, const bool bFixScale,
+                     std::vector<LoopBowCandidate<A>>& out) {
+    using KeyFrame = typename A::KeyFrame;
+    using MapPoint = typename A::MapPoint;
+    const size_t nc = vpCandidates.size();
+    const std::vector<MapPoint*> mps1 = A::MapPointMatches(pCurrentKF);
+    const int n1 = (int)mps1.size();
+    out.clear();
+    out.resize(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        out[c].vpMatchedPoints.assign(n1, static_cast<MapPoint*>(nullptr));
+        out[c].vpKeyFrameMatchedMP.assign(n1, static_cast<KeyFrame*>(nullptr));
+        out[c].vnMatches.assign(c < vvpCovKFi.size() ? vvpCovKFi[c].size() : 0, 0);
+    }
+    if (nc == 0 || vvpCovKFi.size() != nc) return nc == 0;
+    // the pairs, candidate after candidate; a skipped window keyframe keeps its place with pair_ok = 0
+    std::vector<KeyFrame*> pair_kf, live;
+    std::vector<uint8_t> pair_ok;
+    std::vector<int32_t> group(1, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        for (KeyFrame* k : vvpCovKFi[c]) {
+            const bool ok = k && !A::IsBad(k);
+            pair_kf.push_back(k);
+            pair_ok.push_back(ok ? 1 : 0);
+            if (ok) live.push_back(k);
+        }
+        group.push_back((int32_t)pair_kf.size());
+    }
+    const size_t P = pair_kf.size();
+    std::vector<int32_t> live_rows, live_counts;
+    if (!matcherBoW.SearchByBoWIndices(pCurrentKF, live, live_rows, live_counts)) return false;  // :840-851
+    const int C = n1 > 0 ? n1 : 1;
+    std::vector<int32_t> rows(P * (size_t)C + 1, -1);
+    // (the search's rows are as long as the keyframe's feature count, which is the map-point vector's length)
+    const size_t ls = live.empty() ? 0 : (live_rows.size() - 1) / live.size();
+    for (size_t p = 0, l = 0; p < P; ++p) {
+        if (!pair_ok[p]) continue;
+        std::copy(live_rows.begin() + l * ls, live_rows.begin() + l * ls + std::min(ls, (size_t)n1), rows.begin() + p * (size_t)C);
+        for (size_t c = 0; c < nc; ++c)
+            if ((int32_t)p >= group[c] && (int32_t)p < group[c + 1]) out[c].vnMatches[p - group[c]] = live_counts[l];
+        ++l;
+    }
+    // the map points as indices into one pool
+    std::map<MapPoint*, int32_t> ids;
+    std::vector<MapPoint*> pool;
+    std::vector<float> xyz;
+    std::vector<uint8_t> bad;
+    auto id_of = [&](MapPoint* p) -> int32_t {
+        if (!p) return -1;
+        auto it = ids.find(p);
+        if (it != ids.end()) return it->second;
+        const int32_t id = (int32_t)pool.size();
+        ids[p] = id;
+        pool.push_back(p);
+        float X[3];
+        A::WorldPos(p, X);
+        xyz.insert(xyz.end(), X, X + 3);
+        bad.push_back(A::IsBad(p) ? 1 : 0);
+        return id;
+    };
+    struct Store {
+        std::vector<int32_t> mp_id;
+        std::vector<uint8_t> obs_ok;
+    };
+    auto describe = [&](KeyFrame* k, const std::vector<MapPoint*>& mps, Store& s, orb_loop_bow_kf_t& r) {
+        const int n = (int)mps.size();
+        s.mp_id.assign(n > 0 ? n : 1, -1);
+        s.obs_ok.assign(n > 0 ? n : 1, 0);
+        for (int i = 0; i < n; ++i) {
+            s.mp_id[i] = id_of(mps[i]);
+            s.obs_ok[i] = (mps[i] && A::IndexInKeyFrame(mps[i], k) >= 0) ? 1 : 0;  // Sim3Solver.cc:87-91
+        }
+        r.n = n;
+        r.mp_id = s.mp_id.data();
+        r.kps = A::KeysUn(k);
+        r.obs_ok = s.obs_ok.data();
+        r.nlevels = 1;
+        for (int l = 0; l < 12; ++l) r.level_sigma2[l] = 0.f;
+    };
+    orb_loop_bow_in_t in{};
+    Store s1;
+    describe(pCurrentKF, mps1, s1, in.kf1);
+    std::vector<Store> s2(P);
+    std::vector<orb_loop_bow_kf_t> kf2s(P + 1);
+    auto sigma = [](KeyFrame* k, const std::vector<MapPoint*>& mps, orb_loop_bow_kf_t& r) {
+        int top = 0;  // mvLevelSigma2's length is not known here: the levels the keyframe's keypoints use (<= 12)
+        for (int i = 0; i < (int)mps.size(); ++i) top = std::max(top, std::min(11, std::max(0, (int)A::KeysUn(k)[i].octave)));
+        for (int l = 0; l <= top; ++l) r.level_sigma2[l] = A::LevelSigma2(k)[l];
+        r.nlevels = top + 1;
+    };
+    sigma(pCurrentKF, mps1, in.kf1);
+    for (size_t p = 0; p < P; ++p) {
+        kf2s[p].nlevels = 1;
+        if (!pair_ok[p]) continue;
+        const std::vector<MapPoint*> mps = A::MapPointMatches(pair_kf[p]);
+        describe(pair_kf[p], mps, s2[p], kf2s[p]);
+        sigma(pair_kf[p], mps, kf2s[p]);
+    }
+    std::vector<uint8_t> ok1(C, 0);
+    for (int i = 0; i < n1; ++i) ok1[i] = (mps1[i] && !A::IsBad(mps1[i])) ? 1 : 0;
+    in.ok1 = ok1.data();
+    float R[9], t[3];
+    A::Pose(pCurrentKF, R, t);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) in.Tcw1[4 * r + c] = R[3 * r + c];
+        in.Tcw1[4 * r + 3] = t[r];
+    }
+    std::vector<float> Tcw2(12 * nc);
+    for (size_t c = 0; c < nc; ++c) {
+        A::Pose(vpCandidates[c], R, t);
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) Tcw2[12 * c + 4 * r + k] = R[3 * r + k];
+            Tcw2[12 * c + 4 * r + 3] = t[r];
+        }
+    }
+    if (xyz.empty()) xyz.assign(3, 0.f);
+    in.n_pairs = (int32_t)P;
+    in.n_cand = (int32_t)nc;
+    in.kf2s = kf2s.data();
+    in.pair_ok = pair_ok.empty() ? nullptr : pair_ok.data();
+    in.group = group.data();
+    in.Tcw2 = Tcw2.data();
+    in.n_points = (int32_t)pool.size();
+    in.xyz = xyz.data();
+    in.bad = bad.empty() ? nullptr : bad.data();
+    in.matches12 = rows.data();
+    in.stride = C;
+    std::vector<int32_t> mpt(nc * (size_t)C), mpr(nc * (size_t)C), idx1(nc * (size_t)C), num_bow(nc), n(nc);
+    std::vector<float> x1(3 * nc * (size_t)C), x2(3 * nc * (size_t)C), e1(nc * (size_t)C), e2(nc * (size_t)C);
+    orb_loop_bow_out_t o{mpt.data(), mpr.data(), num_bow.data(), n.data(), idx1.data(), x1.data(), x2.data(), e1.data(),
+                         e2.data()};
+    if (detail::Failed(orb_loop_bow_problems(matcherBoW.LibraryHandle(), &in, &o), "orb_loop_bow_problems")) return false;
+    for (size_t c = 0; c < nc; ++c) {
+        const size_t row = c * (size_t)C;
+        for (int k = 0; k < n1; ++k) {
+            const int32_t id = mpt[row + k], j = mpr[row + k];
+            if (id < 0 || id >= (int32_t)pool.size() || j < 0 || j >= group[c + 1] - group[c]) continue;
+            out[c].vpMatchedPoints[k] = pool[id];                  // :876
+            out[c].vpKeyFrameMatchedMP[k] = vvpCovKFi[c][j];       // :878
+        }
+        out[c].numBoWMatches = num_bow[c];
+        out[c].solver.reset(new Sim3Solver<A>(pCurrentKF, vpCandidates[c], n1, n[c], &idx1[row], &x1[3 * row], &x2[3 * row],
+                                              &e1[row], &e2[row], bFixScale));
+    }
+    return true;
+}
+
 }  // namespace orbgpu
 
 /* ---- the accessor for the reference's own classes (compiled inside the reference build) ---------------------- */
@@ -336,6 +535,7 @@ struct ORBSLAM3Sim3Access {
     static Vector3f Vector3(const float v[3]) { return Vector3f(v[0], v[1], v[2]); }
     static std::vector<MapPoint*> MapPointMatches(KeyFrame* k) { return k->GetMapPointMatches(); }
     static bool IsBad(MapPoint* p) { return p->isBad(); }
+    static bool IsBad(KeyFrame* k) { return k->isBad(); }
     static int IndexInKeyFrame(MapPoint* p, KeyFrame* k) { return std::get<0>(p->GetIndexInKeyFrame(k)); }
     static const orb_keypoint_t* KeysUn(KeyFrame* k) { return reinterpret_cast<const orb_keypoint_t*>(k->mvKeysUn.data()); }
     static const float* LevelSigma2(KeyFrame* k) { return k->mvLevelSigma2.data(); }

@@ -11,10 +11,11 @@ from .keyframe import DeviceKeyFrame, Frame, FusePoints, KeyFrame, LocalMapPoint
 from .matcher import ORB_S3P_CLAIM_INVZ, ORB_S3P_CLAIM_PROJECT, ORB_S3P_FUSE, ORBmatcher, sim3_pose
 from .optimizer import LocalBA, local_bundle_adjustment, optimize_sim3, pose_optimization
 from . import distributed, timers
-from .sim3 import Sim3Problem, Sim3Solver, draw_samples, ransac_max_its
+from .sim3 import (LoopBowKeyFrame, Sim3Problem, Sim3Solver, draw_samples, loop_bow_problems, loop_bow_sim3_problems,
+                   ransac_max_its)
 from .stereo import compute_stereo_matches, compute_stereo_matches_batch_device
 from .tracking import (DeviceFrame, DeviceLastPoints, DeviceLocalMap, TrackingChain, TrackingChainBatch,
                        TrackReferenceKeyFrame)
 from .vocabulary import ORBVocabulary
 
-__all__ = ["ORBextractor", "ORBmatcher", "sim3_pose", "ORB_S3P_CLAIM_PROJECT", "ORB_S3P_CLAIM_INVZ", "ORB_S3P_FUSE", "KeyFrame", "Frame", "FusePoints", "LocalMapPoints", "LocalBA", "local_bundle_adjustment", "pose_optimization", "optimize_sim3", "compute_stereo_matches", "compute_stereo_matches_batch_device", "ORBVocabulary", "frustum_frame", "is_in_frustum", "KEYPOINT_DTYPE", "OrbGpuError", "keypoints_to_structured", "undistort_keypoints_device", "DeviceFrame", "DeviceLastPoints", "DeviceLocalMap", "TrackingChain", "TrackingChainBatch", "TrackReferenceKeyFrame", "Sim3Problem", "Sim3Solver", "draw_samples", "ransac_max_its", "_lib"]
+__all__ = ["ORBextractor", "ORBmatcher", "sim3_pose", "ORB_S3P_CLAIM_PROJECT", "ORB_S3P_CLAIM_INVZ", "ORB_S3P_FUSE", "KeyFrame", "Frame", "FusePoints", "LocalMapPoints", "LocalBA", "local_bundle_adjustment", "pose_optimization", "optimize_sim3", "compute_stereo_matches", "compute_stereo_matches_batch_device", "ORBVocabulary", "frustum_frame", "is_in_frustum", "KEYPOINT_DTYPE", "OrbGpuError", "keypoints_to_structured", "undistort_keypoints_device", "DeviceFrame", "DeviceLastPoints", "DeviceLocalMap", "TrackingChain", "TrackingChainBatch", "TrackReferenceKeyFrame", "Sim3Problem", "Sim3Solver", "draw_samples", "ransac_max_its", "LoopBowKeyFrame", "loop_bow_problems", "loop_bow_sim3_problems", "_lib"]

@@ -70,6 +70,25 @@ class Sim3Out(ctypes.Structure):  # orb_sim3_out_t
                 ("hyp_mask", ctypes.c_void_p)]
 
 
+class LoopBowKf(ctypes.Structure):  # orb_loop_bow_kf_t
+    _fields_ = [("n", ctypes.c_int32), ("mp_id", ctypes.c_void_p), ("kps", ctypes.c_void_p), ("obs_ok", ctypes.c_void_p),
+                ("nlevels", ctypes.c_int32), ("level_sigma2", ctypes.c_float * 12)]
+
+
+class LoopBowIn(ctypes.Structure):  # orb_loop_bow_in_t
+    _fields_ = [("kf1", LoopBowKf), ("ok1", ctypes.c_void_p), ("Tcw1", ctypes.c_float * 12), ("n_pairs", ctypes.c_int32),
+                ("n_cand", ctypes.c_int32), ("kf2s", ctypes.c_void_p), ("pair_ok", ctypes.c_void_p),
+                ("group", ctypes.c_void_p), ("Tcw2", ctypes.c_void_p), ("n_points", ctypes.c_int32),
+                ("xyz", ctypes.c_void_p), ("bad", ctypes.c_void_p), ("matches12", ctypes.c_void_p),
+                ("stride", ctypes.c_int32)]
+
+
+class LoopBowOut(ctypes.Structure):  # orb_loop_bow_out_t
+    _fields_ = [("matched_point", ctypes.c_void_p), ("matched_pair", ctypes.c_void_p), ("num_bow", ctypes.c_void_p),
+                ("n", ctypes.c_void_p), ("idx1", ctypes.c_void_p), ("x3dc1", ctypes.c_void_p), ("x3dc2", ctypes.c_void_p),
+                ("max_err1", ctypes.c_void_p), ("max_err2", ctypes.c_void_p)]
+
+
 class OptSim3Problem(ctypes.Structure):  # orb_optsim3_problem_t
     _fields_ = [("n", ctypes.c_int32), ("p1c", ctypes.c_void_p), ("p2c", ctypes.c_void_p), ("obs1", ctypes.c_void_p),
                 ("obs2", ctypes.c_void_p), ("inv_sigma2_1", ctypes.c_void_p), ("inv_sigma2_2", ctypes.c_void_p),
@@ -128,6 +147,10 @@ PROTOTYPES = {
     "orb_search_for_triangulation_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "orb_search_by_bow": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "orb_search_by_bow_device": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "orb_search_by_bow_kf": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "orb_search_by_bow_kf_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "orb_loop_bow_problems": (_i, [_vp, _vp, _vp]),
+    "orb_loop_bow_problems_device": (_i, [_vp, _vp, _vp, _vp]),
     "orb_fuse": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp]),
     "orb_fuse_device": (_i, [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "orb_sim3_projection": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

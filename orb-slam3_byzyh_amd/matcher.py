@@ -185,6 +185,69 @@ class ORBmatcher:
               "orb_search_by_bow_device")
         return out
 
+    def SearchByBoWKF(self, pKF1: KeyFrame, pKF2: KeyFrame, ok1=None, ok2=None):
+        """SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12) (src/ORBmatcher.cc:893-1044),
+        single camera.  ok1[i] / ok2[i]: the keyframe's map point i is non-NULL and not isBad() (None: its
+        has_mappoint).  Returns (nmatches, matches12 int32[pKF1.N]) with matches12[idx1] = the feature of pKF2 whose
+        map point vpMatches12[idx1] receives (-1: NULL)."""
+        (n, m), = self.SearchByBoWKFMany(pKF1, [pKF2], ok1, None if ok2 is None else [ok2])
+        return n, m
+
+    def SearchByBoWKFMany(self, pKF1: KeyFrame, kfs2, ok1=None, ok2=None):
+        """SearchByBoW of pKF1 against every keyframe in `kfs2` in one device launch (the window loop of
+        LoopClosing::DetectCommonRegionsFromBoW, src/LoopClosing.cc:840-851).  ok2: per keyframe a flag array or
+        None.  Returns [(nmatches, matches12)]."""
+        kfs2 = list(kfs2)
+        p = len(kfs2)
+        if p == 0:
+            return []
+        views = (KfView * p)(*[k.view() for k in kfs2])
+        a1 = None if ok1 is None else np.ascontiguousarray(ok1, dtype=np.uint8)
+        oks = [None] * p if ok2 is None else [None if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+                                              for a in ok2]
+        if (a1 is not None and len(a1) != pKF1.N) or len(oks) != p or \
+                any(a is not None and len(a) != k.N for a, k in zip(oks, kfs2)):
+            raise ValueError("ok1: pKF1.N flags; ok2: one array of pKF2.N flags (or None) per keyframe")
+        okp = (ctypes.c_void_p * p)(*[None if a is None else a.ctypes.data for a in oks])
+        m = np.full((p, max(pKF1.N, 1)), -1, np.int32)
+        cnt = np.zeros(p, np.int32)
+        check(_lib.load().orb_search_by_bow_kf(self._handle(), ctypes.byref(pKF1.view()),
+                                               None if a1 is None else a1.ctypes.data, views, okp, p, m.ctypes.data,
+                                               cnt.ctypes.data), "orb_search_by_bow_kf")
+        return [(int(cnt[i]), m[i, :pKF1.N]) for i in range(p)]
+
+    def SearchByBoWKFDevice(self, kf1s, kfs2, pair_kf1=None, ok1=None, ok2=None, stream=None, out=None):
+        """SearchByBoW(KF1, KF2) on device-resident sides (orb_search_by_bow_kf_device): pair p matches
+        kf1s[pair_kf1[p]] (a single DeviceKeyFrame or a list; pair_kf1 None: kf1s[0]) against kfs2[p].  ok1: per
+        kf1 a uint8 CUDA tensor of cap flags or None (its has_mappoint); ok2: the same per pair.  Returns
+        (matches12 [P, C] int32, counts [P] int32) CUDA tensors, C = max cap of the kf1s; a side flagged
+        ORB_ERR_CAPACITY gives that count and an all -1 row.  Asynchronous on `stream`."""
+        import torch
+        kf1s = [kf1s] if isinstance(kf1s, DeviceKeyFrame) else list(kf1s)
+        kfs2 = list(kfs2)
+        n1, p = len(kf1s), len(kfs2)
+        dev = kf1s[0]._keep[0].device
+        C = max(k.cap for k in kf1s)
+        if out is None:
+            out = (torch.empty((max(p, 1), C), dtype=torch.int32, device=dev),
+                   torch.empty(max(p, 1), dtype=torch.int32, device=dev))
+        if p == 0:
+            return out
+        v1 = (KfDeviceView * n1)(*[k.view() for k in kf1s])
+        v2 = (KfDeviceView * p)(*[k.view() for k in kfs2])
+        o1 = [None] * n1 if ok1 is None else list(ok1)
+        o2 = [None] * p if ok2 is None else list(ok2)
+        if len(o1) != n1 or len(o2) != p:
+            raise ValueError("ok1: one entry per kf1; ok2: one entry per pair")
+        p1 = (ctypes.c_void_p * n1)(*[None if a is None else a.data_ptr() for a in o1])
+        p2 = (ctypes.c_void_p * p)(*[None if a is None else a.data_ptr() for a in o2])
+        pk = None if pair_kf1 is None else (ctypes.c_int32 * p)(*[int(i) for i in pair_kf1])
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        check(_lib.load().orb_search_by_bow_kf_device(self._handle(), v1, n1, p1, v2, p2, pk, p, out[0].data_ptr(),
+                                                      out[1].data_ptr(), ctypes.c_void_p(st.cuda_stream)),
+              "orb_search_by_bow_kf_device")
+        return out
+
     def Fuse(self, kfs, points: FusePoints, th: float = 3.0, skip=None):
         """The search half of ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:
         1356-1506) for every keyframe of `kfs` (a Frame carrying Ow / mvInvLevelSigma2 / mfLogScaleFactor, or a

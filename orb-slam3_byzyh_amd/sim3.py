@@ -92,6 +92,109 @@ def _ptr(a):
     return a.data_ptr() if _is_torch(a) else a.ctypes.data
 
 
+class LoopBowKeyFrame:
+    """What loop_bow_problems reads of a keyframe: mp_id [n] int32 (the feature's map point as an index into the
+    pool, -1: NULL), kps (mvKeysUn: a KEYPOINT_DTYPE array, or a [n, 7] float32 CUDA tensor in the extractor's
+    layout), level_sigma2 (mvLevelSigma2, host) and optionally obs_ok [n] uint8 (the point's
+    GetIndexInKeyFrame(this keyframe) >= 0).  numpy arrays for the host form, CUDA tensors for the device form."""
+
+    def __init__(self, mp_id, kps, level_sigma2, obs_ok=None):
+        self.device = _is_torch(mp_id)
+        if self.device:
+            import torch
+            self.mp_id = mp_id.to(torch.int32).contiguous()
+            self.kps = kps.contiguous()
+            self.obs_ok = None if obs_ok is None else obs_ok.to(torch.uint8).contiguous()
+        else:
+            self.mp_id = np.ascontiguousarray(mp_id, np.int32)
+            self.kps = np.ascontiguousarray(kps, _lib.KEYPOINT_DTYPE)
+            self.obs_ok = None if obs_ok is None else np.ascontiguousarray(obs_ok, np.uint8)
+        self.n = int(self.mp_id.shape[0])
+        if int(self.kps.shape[0]) != self.n or (self.obs_ok is not None and int(self.obs_ok.shape[0]) != self.n):
+            raise ValueError("LoopBowKeyFrame: mp_id, kps and obs_ok hold one entry per feature")
+        self.level_sigma2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if not 1 <= len(self.level_sigma2) <= 12:
+            raise ValueError("LoopBowKeyFrame: 1 to 12 pyramid levels")
+
+    def record(self) -> "_lib.LoopBowKf":
+        s2 = (ctypes.c_float * 12)(*[float(x) for x in self.level_sigma2])
+        return _lib.LoopBowKf(self.n, _ptr(self.mp_id), _ptr(self.kps), _ptr(self.obs_ok), len(self.level_sigma2), s2)
+
+
+def loop_bow_problems(matcher, kf1: LoopBowKeyFrame, Tcw1, kfs2, group, Tcw2, xyz, matches12, ok1=None, bad=None,
+                      pair_ok=None, stream=None):
+    """The merge of the window's SearchByBoW matches (src/LoopClosing.cc:855-881) and the Sim3Solver constructor's
+    gather (src/Sim3Solver.cc:71-118) for every candidate in one call (orb_loop_bow_problems[_device]; DESIGN.md
+    section 4p).  kf1: the current keyframe, kfs2: the window keyframes candidate after candidate (LoopBowKeyFrame),
+    group [n_cand + 1]: candidate c owns pairs group[c] .. group[c+1]-1, Tcw1 [3, 4] and Tcw2 [n_cand, 3, 4]: the poses
+    of the current keyframe and of the candidates, xyz [n_points, 3] / bad [n_points]: the map-point pool,
+    matches12 [n_pairs, C]: the rows of SearchByBoWKFMany / SearchByBoWKFDevice, ok1 [kf1.n] (None: from mp_id and
+    bad), pair_ok [n_pairs] (host; 0: the window keyframe is NULL or bad).
+
+    numpy arrays take the host form, CUDA tensors the device form (asynchronous on `stream`, the results are
+    CUDA tensors).  Returns a dict: matched_point, matched_pair, idx1 [n_cand, C] int32, num_bow, n [n_cand] int32,
+    x3dc1, x3dc2 [n_cand, C, 3] float32, max_err1, max_err2 [n_cand, C] float32; entry i < n[c] of row c is the
+    reference's i-th correspondence."""
+    lib = _lib.load()
+    kfs2 = list(kfs2)
+    device = _is_torch(matches12)
+    if any(k.device != device for k in [kf1] + kfs2) or _is_torch(xyz) != device:
+        raise TypeError("loop_bow_problems: numpy arrays or CUDA tensors, not a mixture")
+    group = np.ascontiguousarray(group, np.int32)
+    n_cand, n_pairs = len(group) - 1, len(kfs2)
+    Tcw2 = np.ascontiguousarray(Tcw2, np.float32).reshape(max(n_cand, 0), 12)
+    pok = None if pair_ok is None else np.ascontiguousarray(pair_ok, np.uint8)
+    if pok is not None and len(pok) != n_pairs:
+        raise ValueError("pair_ok: one flag per pair")
+    if device:
+        import torch
+        i32 = lambda a: a.to(torch.int32).contiguous()  # noqa: E731
+        u8 = lambda a: None if a is None else a.to(torch.uint8).contiguous()  # noqa: E731
+        xyz = xyz.to(torch.float32).contiguous()
+    else:
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)  # noqa: E731
+        u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)  # noqa: E731
+        xyz = np.ascontiguousarray(xyz, np.float32)
+    matches12, ok1, bad = i32(matches12), u8(ok1), u8(bad)
+    C = int(matches12.shape[1]) if matches12.ndim == 2 else 0
+    if matches12.ndim != 2 or int(matches12.shape[0]) < n_pairs or (ok1 is not None and int(ok1.shape[0]) < kf1.n) or \
+            (bad is not None and int(bad.shape[0]) != int(xyz.shape[0])):
+        raise ValueError("loop_bow_problems: matches12 [n_pairs, C], ok1 [kf1.n], bad [n_points]")
+    shapes = {"matched_point": ((n_cand, C), "int32"), "matched_pair": ((n_cand, C), "int32"),
+              "num_bow": ((n_cand,), "int32"), "n": ((n_cand,), "int32"), "idx1": ((n_cand, C), "int32"),
+              "x3dc1": ((n_cand, C, 3), "float32"), "x3dc2": ((n_cand, C, 3), "float32"),
+              "max_err1": ((n_cand, C), "float32"), "max_err2": ((n_cand, C), "float32")}
+    if device:
+        # (the library writes every element of all nine: no fill)
+        res = {k: torch.empty(s, dtype=getattr(torch, d), device=matches12.device) for k, (s, d) in shapes.items()}
+    else:
+        res = {k: np.zeros(s, d) for k, (s, d) in shapes.items()}
+    recs = (_lib.LoopBowKf * max(n_pairs, 1))(*[k.record() for k in kfs2])
+    arg = _lib.LoopBowIn(kf1.record(), _ptr(ok1), (ctypes.c_float * 12)(*np.asarray(Tcw1, np.float32).reshape(12)),
+                         n_pairs, n_cand, ctypes.cast(recs, ctypes.c_void_p), _ptr(pok), _ptr(group), _ptr(Tcw2),
+                         int(xyz.shape[0]), _ptr(xyz), _ptr(bad), _ptr(matches12), C)
+    out = _lib.LoopBowOut(*[_ptr(res[k]) for k in ("matched_point", "matched_pair", "num_bow", "n", "idx1", "x3dc1",
+                                                   "x3dc2", "max_err1", "max_err2")])
+    if device:
+        if stream is None:
+            stream = torch.cuda.current_stream(matches12.device).cuda_stream
+        _lib.check(lib.orb_loop_bow_problems_device(matcher._handle(), ctypes.byref(arg), ctypes.byref(out),
+                                                    ctypes.c_void_p(stream)), "orb_loop_bow_problems_device")
+    else:
+        _lib.check(lib.orb_loop_bow_problems(matcher._handle(), ctypes.byref(arg), ctypes.byref(out)),
+                   "orb_loop_bow_problems")
+    return res
+
+
+def loop_bow_sim3_problems(res, n, samples, cam1, cams2, fix_scale, min_inliers):
+    """The Sim3Problem records of loop_bow_problems' result, one per candidate, for Sim3Solver: n[c] (read back
+    by the caller, who draws samples[c] [n_hyp, 3] from it), cam1 and cams2[c] (fx, fy, cx, cy of the current
+    keyframe and of candidate c).  The arrays are views of `res`: nothing is copied."""
+    return [Sim3Problem(res["x3dc1"][c, :int(n[c])], res["x3dc2"][c, :int(n[c])], res["max_err1"][c, :int(n[c])],
+                        res["max_err2"][c, :int(n[c])], cam1, cams2[c], fix_scale, min_inliers, samples[c])
+            for c in range(len(samples))]
+
+
 class Sim3Solver:
     """run(): one dict per problem with hyp_inliers [n_hyp], hyp_t12 [n_hyp, 12] (rows of [s R | t]), hyp_scale
     [n_hyp], winner (the first hypothesis with more than min_inliers inliers, or -1), best (the last hypothesis
